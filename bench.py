@@ -17,7 +17,14 @@ bytes: the u64 line index counts only when the run wrote it (klf_result_index_mo
 runs that index only their tail windows (literal sets) or nothing (-l only) report a second
 timing with KLF_FILTER_FULL_INDEX beside it.
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]; for N > 1 the driver runs
+A plain run does only what the headline needs: it loads the batch, warms up, times the
+steps, writes the last timed step's outputs under --dump-outputs DIR, and prints the line.
+Everything else lives behind --full: the other configs, the full-index second timing, the
+one-shot (cold) cost, the checks against the C oracle, the stage split, the CPU baseline,
+the card's state and the box probe, the committed rocprof evidence.
+
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--full] [--dump-outputs DIR]; for
+N > 1 the driver runs
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`.
 """
 from __future__ import annotations
@@ -217,15 +224,51 @@ def step_bytes(n_in: int, tot: dict, n_streams: int, has_patterns: bool, index_f
     return b
 
 
+# ---------------------------------------------------------------- outputs -----------
+DUMP_CAPS = {"out_bytes": 6 << 20, "line_offsets": 2 << 20, "match_bits": 4 << 20}  # entries: 56 MiB in all
+
+
+def dump_outputs(r, n_streams: int, ddir: str, suffix: str = "") -> None:
+    """--dump-outputs: what a caller of the timed path receives from result `r` (the last
+    timed step's), as DIR/<name>.npy: `counts` (float64 [streams, 6]: lines, parsed, since_ok,
+    matched, selected, out_bytes), `out_bytes` (float32: every stream's selected bytes, in
+    stream order), `line_offsets` (float64: every stream's u64 line offsets, exact below
+    2^53) and `match_bits` (float32: the match bitmaps' bytes).  An array longer than its
+    DUMP_CAPS entry is cut to a fixed sample of its positions (seeded by its length alone, in
+    ascending order), so two builds that compute the same arrays write the same files."""
+    os.makedirs(ddir, exist_ok=True)
+    outs, counts, lines, bits = [], [], [], []
+    for i in range(n_streams):
+        so = r.stream(i)
+        outs.append(so.out)
+        counts.append([so.counts[k] for k in ("lines", "parsed", "since_ok", "matched", "selected", "out_bytes")])
+        lines.append(r.lines(i))
+        bits.append(r.match_bits(i))
+
+    def sample(a, cap):
+        if a.size <= cap:
+            return a
+        return a[np.sort(np.random.default_rng(a.size).choice(a.size, cap, replace=False))]
+    arrays = {"counts": np.array(counts, dtype=np.float64).reshape(n_streams, 6),
+              "out_bytes": sample(np.frombuffer(b"".join(outs), dtype=np.uint8), DUMP_CAPS["out_bytes"])
+              .astype(np.float32),
+              "line_offsets": sample(np.concatenate(lines), DUMP_CAPS["line_offsets"]).astype(np.float64),
+              "match_bits": sample(np.frombuffer(b"".join(bits), dtype=np.uint8), DUMP_CAPS["match_bits"])
+              .astype(np.float32)}
+    for k, a in arrays.items():
+        np.save(os.path.join(ddir, f"{k}{suffix}.npy"), a)
+    log(f"[dump] {sum(a.nbytes for a in arrays.values())} B of outputs under {ddir}")
+
+
 # ---------------------------------------------------------------- one config (N = 1) -
-def run_config(name: str, args, local: int, now: int, headline: bool = False) -> dict:
+def run_config(name: str, args, local: int, now: int, headline: bool = False, dump_dir=None) -> dict:
     sizes, kind, pats, permille, mode, desc = config_table(name)
     t = time.time()
     dev, seg_base, lens = load_batch(sizes, kind, permille, list(range(len(sizes))), local)
     log(f"[{name}] generated + uploaded {sum(lens)} B in {time.time() - t:.1f}s")
     since, tail = ((None, -1) if mode == "-l" else ((now - SINCE_S, 0), TAIL))
     stream = torch.cuda.current_stream()
-    state0 = gpu_state(local)
+    state0 = gpu_state(local) if args.full else None
     eng = E.Engine(local, hip_stream=stream.cuda_stream, **pats)
     ptr = dev.data_ptr()
     n = sum(lens)
@@ -290,6 +333,14 @@ def run_config(name: str, args, local: int, now: int, headline: bool = False) ->
                               + (" + 8 (L + S) u64 line index (written by the run)" if index_mode == "full" else
                                  " (the u64 line index is not written by this run: see full_index)"))
     out["matched_lines"], out["selected_lines"], out["out_bytes"] = tot["matched"], tot["selected"], tot["out_bytes"]
+    if dump_dir:
+        dump_outputs(last, len(lens), dump_dir)
+    if not args.full:  # a plain run: the timed steps (and their outputs) only
+        last.free()
+        eng.close()
+        del dev
+        torch.cuda.empty_cache()
+        return out
     # the step that writes every line's u64 offset too (KLF_FILTER_FULL_INDEX), beside it
     if index_mode != "full":
         last.free()
@@ -627,8 +678,10 @@ def run_sharded(name: str, args, world: int, rank: int, local: int, coll_dev, no
     index_mode = last.index_mode()
     n_mine = sum(lens)
     scan_avg = max(float(np.mean(scan_ms)), 1e-9)
+    if args.dump_outputs and name == HEADLINE:
+        dump_outputs(last, len(lens), args.dump_outputs, suffix=f".rank{rank}" if rank else "")
     ver = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         co = oracle()
         rs = co.RegexSet(pats["match"]) if "match" in pats else None
         sn = since if since is not None else co.GO_ZERO_TIME
@@ -733,6 +786,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline's timed steps: the other configs, the full-index "
+                         "timing, the cold run, the checks against the C oracle, the stage split, the CPU "
+                         "baseline, the card's state, the box probe (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs of the headline config as DIR/<name>.npy "
+                         "(dump_outputs; rank k > 0 writes <name>.rank<k>.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-write", action="store_true", help="skip C3's file write path")
@@ -741,6 +801,8 @@ def main():
     ap.add_argument("--extra-configs", default=None,
                     help="comma list ('' = none); default c2,c1,c3,c4 at N = 1, c2,c3 (sharded) at N > 1")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -761,11 +823,11 @@ def main():
     extras = args.extra_configs
     if extras is None:
         extras = "c2,c1,c3,c4" if world == 1 else "c2,c3"
-    extras = [x for x in extras.split(",") if x and x != HEADLINE]
+    extras = [x for x in extras.split(",") if x and x != HEADLINE] if args.full else []
 
-    probe = box_probe(local)
+    probe = box_probe(local) if args.full else None
     if world == 1:
-        head = run_config(HEADLINE, args, local, now, headline=True)
+        head = run_config(HEADLINE, args, local, now, headline=True, dump_dir=args.dump_outputs)
         value, ms = head["value_GBps"], head["ms_per_step"]
         roof = dict(head.pop("roofline"))
         cpu = head.pop("cpu_baseline", None)
@@ -780,10 +842,11 @@ def main():
                 "frac_min_over_ranks": head["scan_frac_min_over_ranks"],
                 "frac_source": "rank 0's k_scan dispatch events (hipExtLaunchKernel), this run"}
         cpu = None  # (rank 0 at N = 1 only)
-    if "read_sum_GBps" in probe:  # the scan against what this box reads at all
+    if probe and "read_sum_GBps" in probe:  # the scan against what this box reads at all
         roof["frac_of_box_read_rate"] = round(roof["achieved"] / probe["read_sum_GBps"], 4)
     roof["traffic"] = None
-    roof.update(committed(HEADLINE, roof["avg_launch_ms"]))
+    if args.full:
+        roof.update(committed(HEADLINE, roof["avg_launch_ms"]))
     # the headline's evidence where the driver keeps it (its record keeps `config` and
     # `roofline`, not `extra`, and cuts long strings): short keys, numbers and flags
     cfg = {"workload": head["workload_short"], "streams": head["streams"], "global_bytes": head["bytes"],
@@ -809,6 +872,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": ms,
         "higher_is_better": True,
         "scaling": "weak",

@@ -12,5 +12,5 @@ tail -1 $out/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 bash scripts/profile_round.sh "$out" trace
 KLF_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 > $out/bench_n2_gloo.json 2> $out/bench_n2_gloo.err
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full > $out/bench_n2_gloo.json 2> $out/bench_n2_gloo.err
 echo "final_round done: $out"

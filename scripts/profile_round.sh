@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 mkdir -p "$out"
 if [ "$what" != pmc ]; then
   timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run \
-    -- python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+    -- python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"
   echo "trace done"
   for c in c5 c2 c3 c4; do  # per-config kernel splits (the bench trace mixes every config)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_$c" -o run \

@@ -6,5 +6,5 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 $o/pytest_gpu.log
 bash scripts/ktrace_ab.sh $o c5 base > $o/kt_c5.txt 2>&1
 bash scripts/ktrace_ab.sh $o c1 base > $o/kt_c1.txt 2>&1
-timeout -k 10 600 python bench.py > $o/bench.json 2> $o/bench.err
+timeout -k 10 600 python bench.py --full > $o/bench.json 2> $o/bench.err
 echo "r6h done"

@@ -7,5 +7,5 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 $o/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1
 tail -1 $o/smoke.log
-timeout -k 10 700 python bench.py > $o/bench.json 2> $o/bench.err
+timeout -k 10 700 python bench.py --full > $o/bench.json 2> $o/bench.err
 echo "r6w done"

@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--probe", action="store_true", help="add bench.box_probe (the box's copy / read rates)")
     a = ap.parse_args()
     ns = argparse.Namespace(steps=a.steps, warmup=a.warmup, no_verify=True, no_write=True, no_capture=True,
-                            no_cpu_baseline=True, capture_piece=4 << 20)
+                            no_cpu_baseline=True, capture_piece=4 << 20, full=True, dump_outputs=None)
     now = bench.synth.T0 + bench.synth.SPAN + 1
     probe = bench.box_probe(0) if a.probe else None
     out = bench.run_config(a.config, ns, 0, now)
