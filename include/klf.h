@@ -159,6 +159,33 @@ int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n_streams,
  * the reference (kubelet applies --tail once, server-side: logs.go / tail.go). */
 int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_result** out);
 
+/* Context lines and inverted match over the latest run (SPEC.md S4a; grep -A / -B / -C and
+ * --invert-match): with S = the run's matching lines M (KLF_REGROUP_INVERT: the parsed lines
+ * outside M), the selection becomes G' = the parsed lines at most `after` lines behind or
+ * `before` lines ahead of a line of S in the same stream (distances count every line, also
+ * unparseable ones; overlapping contexts merge, no separator line, input order), and --since
+ * and the tail rule with `tail` run over G' as they ran over M.  counts.matched = |G'|;
+ * lines / parsed / since_ok do not change.  before = after = 0 without flags is
+ * klf_retail(prev, tail) byte for byte.  Every u32 value is legal (it saturates at the
+ * stream's ends).
+ * The contract is klf_retail's: prev must be the engine's latest result (KLF_ESTATE) and is
+ * stale afterwards; only the match bitmap (L/8 bytes) and the line meta (2 L) are read
+ * again, never the input.  G' always starts from M, so regroups do not compound; a
+ * klf_retail of the new result re-tails over G'; the next klf_run / klf_run_device starts
+ * from its own matches.  KLF_EINVAL: an engine without patterns, o == NULL, tail < -1,
+ * unknown flag bits, _reserved != 0.  Replaces nothing in the reference (its client writes
+ * every line the server sends; the --grep / --match flags are new, cmd/root.go:485-497).
+ * Out of scope: follow sessions (context would have to span flushes; a flush's result
+ * regroups within that flush only) and shard.run_split (context would have to span the
+ * byte-range shards of a stream). */
+#define KLF_REGROUP_INVERT 1u
+typedef struct klf_regroup_opts {
+  uint32_t before, after; /* context lines ahead of / behind a line of S */
+  uint32_t flags;         /* KLF_REGROUP_* bits, 0 = none */
+  uint32_t _reserved;     /* 0 */
+} klf_regroup_opts;
+int klf_regroup(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out);
+
 /* ---- results -------------------------------------------------------------------- */
 /* Selected bytes of one stream (host view, D2H on first access; bytes == NULL: len and
  * counts only, no D2H). */
@@ -172,6 +199,11 @@ int klf_result_lines(klf_result* r, uint32_t stream_id, const uint64_t** off,
 /* Match bitmap of one stream (bit l LSB-first in byte l>>3); *nbytes = ceil(lines/8).
  * Returns KLF_EINVAL when the engine has no patterns. */
 int klf_result_match_bits(klf_result* r, uint32_t stream_id, const uint8_t** bits,
+                          uint64_t* nbytes);
+/* Selection bitmap of one stream, packed like klf_result_match_bits: G' on a result of
+ * klf_regroup (and on a klf_retail of one), M on every other result (klf_result_match_bits
+ * returns M on all of them).  KLF_EINVAL when the engine has no patterns. */
+int klf_result_group_bits(klf_result* r, uint32_t stream_id, const uint8_t** bits,
                           uint64_t* nbytes);
 /* Per-pattern match counts of one stream (SURVEY.md §8a K4/K5 `count[stream][pattern]`, the
  * per-stream record the ranks gather, §8e): counts[p] = parsed lines whose content matches

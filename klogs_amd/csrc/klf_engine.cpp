@@ -242,6 +242,9 @@ struct klf_engine {
   bool graph_off = false;
   hipEvent_t ev[11] = {};  // [7], [8]: k_scan's dispatch (hipExtLaunchKernel start / stop); [9], [10]: k_tcopy's; [6] unused
   klf::RunArgs last_args{};  // arguments of the latest completed run (klf_retail)
+  // klf_regroup: the selection bitmap G' (the layout of d_bits) and the regroup kernels'
+  // chunk summaries; allocated by the first regroup, so a plain run pays nothing for them
+  DevBuf d_gbits, d_gsum;
   // the latest run's global line index is still to be built (lazy index, dense path): the
   // k_scatter launch that builds it
   std::vector<klf::RunArgs> index_pending;
@@ -256,17 +259,22 @@ struct klf_result {
   std::vector<SegOut> so;            // per segment
   std::vector<uint64_t> seg_base;    // per segment (device byte offset)
   bool has_bits = false;
+  bool grouped = false;              // selected over klf_regroup's bitmap (the engine's d_gbits)
   uint64_t total_lines = 0, total_out = 0;
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t ev_mask = 0;              // the timing events the run recorded
   int index_mode = KLF_INDEX_FULL;   // how much of the line index the run itself wrote
   // lazily filled host copies
-  bool have_out = false, have_lines = false, have_bits = false;
+  bool have_out = false, have_lines = false;
   std::vector<uint8_t> out;
   std::vector<uint64_t> line_off;
-  std::vector<uint32_t> bits;
-  std::vector<std::vector<uint8_t>> stream_bits;
-  std::vector<uint8_t> have_stream_bits;
+  // [0] the match bitmap M, [1] a regrouped result's selection bitmap G'
+  struct HostBits {
+    bool have = false;
+    std::vector<uint32_t> bits;
+    std::vector<std::vector<uint8_t>> stream_bits;
+    std::vector<uint8_t> have_stream_bits;
+  } hbits[2];
   // per-pattern counts (KLF_FILTER_PATTERN_COUNTS): [segment][compiled id]
   bool counted = false, pcount_ok = false;
   std::vector<uint32_t> pcount;
@@ -716,7 +724,7 @@ extern "C" void klf_close(klf_engine* e) {
                     &e->d_qf_ent, &e->d_qf_nbytes, &e->d_qf_anc, &e->d_rx_vec4, &e->d_qhits, &e->d_hslots, &e->d_hist, &e->d_hflat, &e->d_cand, &e->d_batch, &e->d_segs, &e->d_tstat,
                     &e->d_slots, &e->d_pool, &e->d_tile_base, &e->d_bsum, &e->d_cstatus, &e->d_counters, &e->d_cmap, &e->d_cseg,
                     &e->d_line_off, &e->d_meta, &e->d_bits, &e->d_wpre, &e->d_out, &e->d_tile_seg, &e->d_mpart, &e->d_trec, &e->d_truns, &e->d_kbase,
-                    &e->d_fext0, &e->d_fext, &e->d_frinfo, &e->d_out2})
+                    &e->d_fext0, &e->d_fext, &e->d_frinfo, &e->d_out2, &e->d_gbits, &e->d_gsum})
     b->release();
   e->d_asm.release();
   e->d_scratch.release();
@@ -1750,10 +1758,12 @@ extern "C" int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n,
 
 static int ensure_index(klf_engine* e);
 
-extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_result** out) {
-  if (!e || !prev || !out || prev->e != e || tail < -1) return KLF_EINVAL;
-  *out = nullptr;
-  if (prev->gen != e->gen || e->last_gen != prev->gen) return set_err(e, KLF_ESTATE, "klf_retail: not the latest run");
+// klf_retail (o null: over the bitmap the latest result was selected from) and klf_regroup
+// (o: over G', built first from the run's match bitmap in d_bits).
+static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
+                       const char* what) {
+  if (prev->gen != e->gen || e->last_gen != prev->gen)
+    return set_err(e, KLF_ESTATE, std::string(what) + ": not the latest run");
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   auto* r = new (std::nothrow) klf_result();
@@ -1763,6 +1773,7 @@ extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_res
   r->seg_of = prev->seg_of;
   r->seg_base = prev->seg_base;
   r->has_bits = prev->has_bits;
+  r->grouped = o ? true : prev->grouped;
   r->total_lines = prev->total_lines;
   r->counted = prev->counted;
   r->pcount_ok = prev->pcount_ok;
@@ -1779,7 +1790,26 @@ extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_res
     a.plan_mode = 0;   // (and may be larger: the gather's plan over the whole grid)
     hipStream_t st = e->stream;
     uint32_t rmask = 0;
-    hipError_t h = klf::launch_retail(a, st, e->ev, e->num_cus, &rmask);
+    hipError_t h = hipSuccess;
+    klf::RegroupArgs g{};
+    if (o) {  // always from M: regroups do not compound
+      const uint64_t nw = a.cap_lines / 32 + 1, nc = a.cap_lines / klf::kMatchChunk + 1;
+      h = e->d_gbits.ensure(nw * 4);
+      if (h == hipSuccess) h = e->d_gsum.ensure(nc * 4 * 8);
+      g.bits_in = e->d_bits.as<uint32_t>();
+      g.bits_out = e->d_gbits.as<uint32_t>();
+      g.meta = a.meta;
+      g.segout = a.segout;
+      g.nsegs = nsegs;
+      g.invert = (o->flags & KLF_REGROUP_INVERT) ? 1u : 0u;
+      g.cap_lines = a.cap_lines;
+      g.before = o->before;
+      g.after = o->after;
+      g.csum = e->d_gsum.as<uint64_t>();
+      g.nchunks = (prev->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;  // (<= nc: lines <= cap_lines)
+      a.bits = g.bits_out;
+    }
+    if (h == hipSuccess) h = klf::launch_retail(a, st, e->ev, e->num_cus, &rmask, o ? &g : nullptr);
     uint32_t short_out = 0;
     if (h == hipSuccess) h = e->h_rb.ensure(kCtrBytes + nsegs * sizeof(SegOut));
     if (h == hipSuccess)
@@ -1792,15 +1822,15 @@ extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_res
     }
     if (h == hipSuccess && short_out) h = grow_out_retail(e, a, r->so);  // a larger window than the buffer holds
     if (h == hipSuccess) e->last_args = a;
-    if (h != hipSuccess) { delete r; return hip_err(e, h, "klf_retail"); }
+    if (h != hipSuccess) { delete r; return hip_err(e, h, what); }
     if ((rmask & 1u) && (rmask >> 5 & 1u)) {
       float ms = 0.f;
-      if ((h = hipEventElapsedTime(&ms, e->ev[0], e->ev[5])) != hipSuccess) { delete r; return hip_err(e, h, "klf_retail timing"); }
+      if ((h = hipEventElapsedTime(&ms, e->ev[0], e->ev[5])) != hipSuccess) { delete r; return hip_err(e, h, "re-tail timing"); }
       r->ms[4] = ms;
     }
     if ((rmask >> 9 & 1u) && (rmask >> 10 & 1u)) {
       float ms = 0.f;
-      if ((h = hipEventElapsedTime(&ms, e->ev[9], e->ev[10])) != hipSuccess) { delete r; return hip_err(e, h, "klf_retail timing"); }
+      if ((h = hipEventElapsedTime(&ms, e->ev[9], e->ev[10])) != hipSuccess) { delete r; return hip_err(e, h, "re-tail timing"); }
       r->ms[7] = ms;
     }
     r->ev_mask = rmask;
@@ -1810,6 +1840,22 @@ extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_res
   e->last_gen = r->gen;
   *out = r;
   return KLF_OK;
+}
+
+extern "C" int klf_retail(klf_engine* e, klf_result* prev, int64_t tail, klf_result** out) {
+  if (!e || !prev || !out || prev->e != e || tail < -1) return KLF_EINVAL;
+  *out = nullptr;
+  return retail_impl(e, prev, nullptr, tail, out, "klf_retail");
+}
+
+extern "C" int klf_regroup(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail,
+                           klf_result** out) {
+  if (!e || !prev || !o || !out || prev->e != e || tail < -1) return KLF_EINVAL;
+  *out = nullptr;
+  if ((o->flags & ~KLF_REGROUP_INVERT) || o->_reserved)
+    return set_err(e, KLF_EINVAL, "klf_regroup: unknown flag bits or a non-zero _reserved");
+  if (!prev->has_bits) return set_err(e, KLF_EINVAL, "klf_regroup: the engine has no patterns");
+  return retail_impl(e, prev, o, tail, out, "klf_regroup");
 }
 
 extern "C" int klf_run(klf_engine* e, const klf_filter* f, klf_result** out) {
@@ -2112,39 +2158,51 @@ extern "C" int klf_result_lines(klf_result* r, uint32_t id, const uint64_t** off
   return KLF_OK;
 }
 
-extern "C" int klf_result_match_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes) {
+// The per-stream packing of one of the run's line bitmaps: which = 0 the match bitmap M
+// (d_bits), 1 a regrouped result's selection bitmap G' (d_gbits).
+static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes, int which) {
   int rc = check_result(r, id);
   if (rc) return rc;
   if (!r->has_bits) return KLF_EINVAL;
   klf_engine* e = r->e;
-  if (!r->have_bits) {
+  auto& hb = r->hbits[which];
+  if (!hb.have) {
     if (int rc2 = ensure_index(e)) return rc2;
     const size_t nw = r->total_lines / 32 + 1;
-    r->bits.assign(nw, 0);
+    hb.bits.assign(nw, 0);
     if (!r->so.empty()) {
-      HIPCHK(e, hipMemcpyAsync(r->bits.data(), e->d_bits.p, nw * 4, hipMemcpyDeviceToHost, e->stream), "D2H bits");
+      const void* src = which ? e->d_gbits.p : e->d_bits.p;
+      HIPCHK(e, hipMemcpyAsync(hb.bits.data(), src, nw * 4, hipMemcpyDeviceToHost, e->stream), "D2H bits");
       HIPCHK(e, hipStreamSynchronize(e->stream), "sync");
     }
-    r->have_bits = true;
-    r->stream_bits.assign(r->n_streams, {});
-    r->have_stream_bits.assign(r->n_streams, 0);
+    hb.have = true;
+    hb.stream_bits.assign(r->n_streams, {});
+    hb.have_stream_bits.assign(r->n_streams, 0);
   }
-  if (!r->have_stream_bits[id]) {
+  if (!hb.have_stream_bits[id]) {
     const int64_t s = r->seg_of[id];
-    auto& v = r->stream_bits[id];
+    auto& v = hb.stream_bits[id];
     if (s >= 0) {
       const uint64_t lo = r->so[s].line_lo, n = r->so[s].line_hi - lo;
       v.assign((n + 7) / 8, 0);
       for (uint64_t i = 0; i < n; ++i) {
         const uint64_t l = lo + i;
-        if ((r->bits[l >> 5] >> (l & 31)) & 1u) v[i >> 3] |= (uint8_t)(1u << (i & 7));
+        if ((hb.bits[l >> 5] >> (l & 31)) & 1u) v[i >> 3] |= (uint8_t)(1u << (i & 7));
       }
     }
-    r->have_stream_bits[id] = 1;
+    hb.have_stream_bits[id] = 1;
   }
-  if (bits) *bits = r->stream_bits[id].data();
-  if (nbytes) *nbytes = r->stream_bits[id].size();
+  if (bits) *bits = hb.stream_bits[id].data();
+  if (nbytes) *nbytes = hb.stream_bits[id].size();
   return KLF_OK;
+}
+
+extern "C" int klf_result_match_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes) {
+  return result_bits(r, id, bits, nbytes, 0);
+}
+
+extern "C" int klf_result_group_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes) {
+  return result_bits(r, id, bits, nbytes, r && r->grouped ? 1 : 0);
 }
 
 extern "C" int klf_result_pattern_counts(klf_result* r, uint32_t id, uint64_t* counts, uint32_t cap, uint32_t* n) {

@@ -2801,6 +2801,195 @@ __global__ __launch_bounds__(256) void k_retail_init(RunArgs a) {
   }
 }
 
+// ============================ regroup: context lines / inverted match (SPEC.md S4a) ==
+// G' = parsed lines within `after` lines behind / `before` lines ahead of a line of S, in
+// the same stream; S = M (the run's match bitmap) or, inverted, the parsed lines outside M.
+// For line l of stream [lo, hi): with P = the last line of S at or before l and N = the
+// first at or after l (over all streams), l is in G' iff it is parsed and
+// (P >= lo and l - P <= after) or (N < hi and N - l <= before): the nearest line of S on
+// either side decides, and one outside the stream means none inside.  Per kMatchChunk lines
+// (256 words, one per thread, like k_mcount):
+//   k_rg_sum    per chunk: the last and first line of S
+//   k_rg_carry  one block: the same over all chunks before / after each chunk
+//   k_rg_build  per chunk: block scans carry P / N from word to word; each word ORs the
+//               carried-in masks with the in-word smear of S, per stream part of the word
+// The cost is L/8 + 2L bytes read and L/8 written whatever before and after are.  Line
+// positions are kept as max-scan keys: P + 1 (0 = none) and ~N (0 = none).
+__device__ __forceinline__ uint64_t wave_incl_scan_max64(uint64_t x, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t o = __shfl_up(x, d, 64);
+    if (lane >= d) x = x > o ? x : o;
+  }
+  return x;
+}
+__device__ __forceinline__ uint64_t wave_incl_rscan_max64(uint64_t x, int lane) {  // over lanes >= lane
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t o = __shfl_down(x, d, 64);
+    if (lane + d < 64) x = x > o ? x : o;
+  }
+  return x;
+}
+// Exclusive block max-scans of x over the threads before (*pre) and after (*post) this one;
+// returns the block maximum.  s_w: [2][4].
+__device__ __forceinline__ void block_excl_scan_max64(uint64_t x, uint64_t y, uint64_t (*s_w)[4], uint64_t* pre,
+                                                      uint64_t* post) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t fi = wave_incl_scan_max64(x, lane), ri = wave_incl_rscan_max64(y, lane);
+  uint64_t fe = __shfl_up(fi, 1, 64), re = __shfl_down(ri, 1, 64);
+  if (lane == 0) fe = 0;
+  if (lane == 63) re = 0;
+  __syncthreads();
+  if (lane == 63) s_w[0][wv] = fi;
+  if (lane == 0) s_w[1][wv] = ri;
+  __syncthreads();
+  for (int k = 0; k < 4; ++k) {
+    if (k < wv) fe = fe > s_w[0][k] ? fe : s_w[0][k];
+    if (k > wv) re = re > s_w[1][k] ? re : s_w[1][k];
+  }
+  *pre = fe;
+  *post = re;
+}
+
+// The parsed bits of word w's 32 lines (16-B loads of their meta; line by line where the
+// word reaches past the line count).
+__device__ __forceinline__ uint32_t parsed_word(const uint16_t* __restrict__ meta, uint64_t w, uint64_t L) {
+  const uint64_t l0 = w * 32;
+  uint32_t p = 0;
+  if (l0 + 32 <= L) {
+    const uint4* q = reinterpret_cast<const uint4*>(meta + l0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 v = q[k];
+      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        p |= ((x[j] & 1u) | ((x[j] >> 15) & 2u)) << (8 * k + 2 * j);
+    }
+  } else {
+    for (uint64_t l = l0; l < L; ++l) p |= (uint32_t)(meta[l] & Meta::kParsed) << (l - l0);
+  }
+  return p;
+}
+// Word w of S (0 past the line count).
+__device__ __forceinline__ uint32_t rg_s_word(const RegroupArgs& g, uint64_t w, uint64_t L) {
+  if (w * 32 >= L) return 0u;
+  const uint32_t m = g.bits_in[w] & word_range_mask(w, 0, L);
+  return g.invert ? parsed_word(g.meta, w, L) & ~m : m;
+}
+// x | x << 1 | ... | x << k (UP) or the same with right shifts, k <= 31: doubling steps.
+template <bool UP>
+__device__ __forceinline__ uint32_t smear(uint32_t x, uint32_t k) {
+  uint32_t cur = 1;
+  while (cur * 2 <= k + 1) {
+    x |= UP ? x << cur : x >> cur;
+    cur *= 2;
+  }
+  const uint32_t r = k + 1 - cur;  // < cur
+  return x | (UP ? x << r : x >> r);
+}
+
+__global__ __launch_bounds__(256) void k_rg_sum(RegroupArgs g) {
+  __shared__ uint64_t s_w[2][4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t;
+    const uint32_t s = rg_s_word(g, w, L);
+    uint64_t last = s ? w * 32 + (31 - __clz(s)) + 1 : 0, first = s ? ~(w * 32 + (__ffs(s) - 1)) : 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint64_t a = __shfl_xor(last, d, 64), b = __shfl_xor(first, d, 64);
+      last = last > a ? last : a;
+      first = first > b ? first : b;
+    }
+    __syncthreads();
+    if (lane == 0) { s_w[0][wv] = last; s_w[1][wv] = first; }
+    __syncthreads();
+    if (t == 0) {
+      uint64_t a = s_w[0][0], b = s_w[1][0];
+      for (int k = 1; k < 4; ++k) {
+        a = a > s_w[0][k] ? a : s_w[0][k];
+        b = b > s_w[1][k] ? b : s_w[1][k];
+      }
+      g.csum[4 * c] = a;
+      g.csum[4 * c + 1] = b;
+    }
+  }
+}
+
+// Thread t owns the chunks [t K, (t + 1) K): their maxima, one block scan, then each chunk's
+// exclusive prefix / suffix.
+__global__ __launch_bounds__(256) void k_rg_carry(RegroupArgs g) {
+  __shared__ uint64_t s_w[2][4];
+  const uint64_t K = (g.nchunks + 255) / 256;
+  const uint64_t c0 = threadIdx.x * K, c1 = c0 + K < g.nchunks ? c0 + K : g.nchunks;
+  uint64_t a = 0, b = 0;
+  for (uint64_t c = c0; c < c1; ++c) {
+    const uint64_t x = g.csum[4 * c], y = g.csum[4 * c + 1];
+    a = a > x ? a : x;
+    b = b > y ? b : y;
+  }
+  uint64_t pre, post;
+  block_excl_scan_max64(a, b, s_w, &pre, &post);
+  for (uint64_t c = c0; c < c1; ++c) {
+    g.csum[4 * c + 2] = pre;
+    const uint64_t x = g.csum[4 * c];
+    pre = pre > x ? pre : x;
+  }
+  for (uint64_t c = c1; c > c0; --c) {
+    g.csum[4 * (c - 1) + 3] = post;
+    const uint64_t y = g.csum[4 * (c - 1) + 1];
+    post = post > y ? post : y;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_rg_build(RegroupArgs g) {
+  __shared__ uint64_t s_w[2][4];
+  const int t = threadIdx.x;
+  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
+  const uint64_t nw = g.cap_lines / 32 + 1;  // words of the bitmaps
+  const uint32_t ka = g.after < 31 ? (uint32_t)g.after : 31u, kb = g.before < 31 ? (uint32_t)g.before : 31u;
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const bool live = l0 < L;
+    uint32_t pw = 0, sw = 0;
+    if (live) {
+      pw = parsed_word(g.meta, w, L);
+      const uint32_t m = g.bits_in[w] & word_range_mask(w, 0, L);
+      sw = g.invert ? pw & ~m : m;
+    }
+    uint64_t pk, nk;  // P + 1 over the words before this one, ~N over the words after it
+    block_excl_scan_max64(sw ? l0 + (31 - __clz(sw)) + 1 : 0, sw ? ~(l0 + (__ffs(sw) - 1)) : 0, s_w, &pk, &nk);
+    const uint64_t cp = g.csum[4 * c + 2], cn = g.csum[4 * c + 3];
+    pk = pk > cp ? pk : cp;
+    nk = nk > cn ? nk : cn;
+    uint32_t out = 0;
+    if (live && pw) {
+      const uint64_t wend = l0 + 32;
+      for (uint32_t s = find_seg_by_line(g.segout, g.nsegs, l0); s < g.nsegs; ++s) {
+        const uint64_t lo = g.segout[s].line_lo, hi = g.segout[s].line_hi;
+        if (lo >= wend) break;
+        const uint32_t pm = word_range_mask(w, lo, hi);
+        const uint32_t sp = sw & pm;
+        uint32_t m = smear<true>(sp, ka) | smear<false>(sp, kb);
+        if (pk && pk - 1 >= lo) {  // (P < l0) the lines up to P + after
+          const uint64_t reach = pk - 1 + g.after;
+          if (reach >= l0) m |= reach - l0 >= 31 ? ~0u : (2u << (reach - l0)) - 1u;
+        }
+        if (nk && ~nk < hi) {  // (N >= l0 + 32) the lines from N - before on
+          const uint64_t n = ~nk, from = n >= g.before ? n - g.before : 0;
+          if (from < wend) m |= from <= l0 ? ~0u : ~0u << (from - l0);
+        }
+        out |= m & pm;
+      }
+      out &= pw;  // (pw has no bit at or past L)
+    }
+    if (w < nw) g.bits_out[w] = out;
+  }
+}
+
 // Zeroes the run's counters and per-stream records (one launch instead of memsets).
 __global__ __launch_bounds__(256) void k_init(RunArgs a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -4611,12 +4800,23 @@ hipError_t launch_tcopy(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int nu
   return hipGetLastError();
 }
 
-hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int num_cus, uint32_t* ev_mask) {
+hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int num_cus, uint32_t* ev_mask,
+                         const RegroupArgs* g) {
   uint32_t m_local = 0;
   uint32_t& m = ev_mask ? *ev_mask : m_local;
   hipError_t e = hipEventRecord(ev[0], st);
   if (e != hipSuccess) return e;
   m |= 1u;
+  if (g) {  // the selection bitmap first (a.bits = g->bits_out)
+    const uint64_t gmax = (uint64_t)num_cus * 16;
+    const uint32_t gc = (uint32_t)(g->nchunks < gmax ? g->nchunks : gmax);
+    hipLaunchKernelGGL(k_rg_sum, dim3(gc), dim3(256), 0, st, *g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rg_carry, dim3(1), dim3(256), 0, st, *g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rg_build, dim3(gc), dim3(256), 0, st, *g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(k_retail_init, dim3((a.nsegs + 255) / 256 < 1024 ? (a.nsegs + 255) / 256 : 1024), dim3(256), 0,
                      st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -361,6 +361,26 @@ struct RunArgs {
   uint64_t* fuse_rinfo;
 };
 
+// Context lines / inverted match over a finished run (klf_regroup, SPEC.md S4a): the
+// regroup kernels read the run's match bitmap M and its line meta and write the selection
+// bitmap G' the tail stage then runs over.  Their own arguments: RunArgs, and with it every
+// kernel of the run itself, stays as it is.
+struct RegroupArgs {
+  const uint32_t* bits_in;  // M, [cap_lines / 32 + 1]
+  uint32_t* bits_out;       // G', same layout
+  const uint16_t* meta;     // [cap_lines]
+  const SegOut* segout;     // [nsegs] (line_lo / line_hi; the line count is the last line_hi)
+  uint32_t nsegs;
+  uint32_t invert;          // S = parsed lines not in M
+  uint64_t cap_lines;
+  uint64_t before, after;   // context lines before / after a line of S
+  // per kMatchChunk chunk c: [0] last line of S in the chunk + 1 (0 = none), [1] ~(its first
+  // line) (0 = none); then the same over the chunks before c ([2]) / after c ([3]);
+  // 4 * nchunks u64, nchunks = cap_lines / kMatchChunk + 1
+  uint64_t* csum;
+  uint64_t nchunks;
+};
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]
@@ -376,8 +396,10 @@ hipError_t launch_scatter(const RunArgs& a, hipStream_t stream, int num_cus);
 hipError_t launch_pipeline(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus, int phase = 0,
                            uint32_t* ev_mask = nullptr);
 // Re-runs matched counts, tail and compaction of the last pipeline with a.tail changed.
+// g (nullable): first builds the selection bitmap g->bits_out (= a.bits) from g->bits_in
+// (k_rg_sum / k_rg_carry / k_rg_build), inside the same ev[0] .. ev[5] bracket.
 hipError_t launch_retail(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus,
-                         uint32_t* ev_mask = nullptr);
+                         uint32_t* ev_mask = nullptr, const RegroupArgs* g = nullptr);
 // Data statistics (kGramHistWords u32, zeroed here) of the first `sample` bytes of each of
 // up to 16 segments: byte counts, and the 2-grams at even offsets (folded like the
 // prefilter's grams).

@@ -2,7 +2,12 @@
 // over captured log bodies, with the filter on the GPU through libklf.
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
+//                [-A N] [-B N] [-C N] [--invert-match]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
+//
+// -A / -B / -C N (lines of context after / before / around a matching line) and
+// --invert-match (the lines that do not match) need a --grep or --match; they are grep's,
+// not the reference's (-v stays its version flag): SPEC.md S4a, klf_regroup.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -52,6 +57,8 @@ bool read_file(const std::string& path, std::vector<uint8_t>& out) {
 void usage() {
   std::fprintf(stderr,
                "usage: klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...\n"
+               "                    [-A N] [-B N] [-C N] [--invert-match]   (with --grep / --match: lines of\n"
+               "                    context after / before / around a match; the lines that do not match)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -65,6 +72,15 @@ int main(int argc, char** argv) {
   int device = 0;
   klf_time now{(int64_t)time(nullptr), 0, 0};
   std::vector<std::string> greps, matches;
+  klf_regroup_opts regroup{0, 0, 0, 0};
+  bool regrouped = false;  // any of -A / -B / -C / --invert-match
+  auto context = [&](const std::string& v) -> uint32_t {
+    char* end = nullptr;
+    const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
+    if (v.empty() || v[0] == '-' || *end) usage();
+    regrouped = true;
+    return x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)x;
+  };
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> std::string {
@@ -77,6 +93,10 @@ int main(int argc, char** argv) {
     else if (a == "-i" || a == "--init") init = true;
     else if (a == "--grep") greps.push_back(val());
     else if (a == "--match") matches.push_back(val());
+    else if (a == "-A" || a == "--after-context") regroup.after = context(val());
+    else if (a == "-B" || a == "--before-context") regroup.before = context(val());
+    else if (a == "-C" || a == "--context") regroup.before = regroup.after = context(val());
+    else if (a == "--invert-match") { regroup.flags |= KLF_REGROUP_INVERT; regrouped = true; }
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -92,6 +112,7 @@ int main(int argc, char** argv) {
     else manifest = a;
   }
   if (manifest.empty()) usage();
+  if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
   if (logpath.empty()) {  // defaultLogPath (:47)
     char buf[128];
     klh_default_log_path(now.sec, buf, sizeof(buf));
@@ -194,8 +215,19 @@ int main(int argc, char** argv) {
       if (!buf.empty() && klf_stage(e, i, buf.data(), buf.size()) != KLF_OK) panic_exit("klf_stage");
     }
     klf_result* r = nullptr;
+    // context / inversion: the run itself with --tail 0 (the cheapest run that leaves the
+    // line index and the match bitmap behind), then klf_regroup applies the user's tail
+    const int64_t user_tail = filter.tail;
+    if (regrouped) filter.tail = 0;
     rc = klf_run(e, &filter, &r);
     if (rc != KLF_OK) panic_exit(std::string("klf_run: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+    if (regrouped) {
+      klf_result* g = nullptr;
+      rc = klf_regroup(e, r, &regroup, user_tail, &g);
+      if (rc != KLF_OK) panic_exit(std::string("klf_regroup: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      klf_result_free(r);
+      r = g;
+    }
     // writeLogToDisk (:359-374): one klf_result_write over every stream's file (chunked,
     // double-buffered D2H from pinned memory), files closed afterwards
     std::vector<int> fds(n, -1);

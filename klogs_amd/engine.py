@@ -55,6 +55,10 @@ class _Filter(C.Structure):
     _fields_ = [("since", _Time), ("tail", C.c_int64), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class _RegroupOpts(C.Structure):
+    _fields_ = [("before", C.c_uint32), ("after", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
 class _Counts(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("parsed", C.c_uint64), ("since_ok", C.c_uint64),
                 ("matched", C.c_uint64), ("selected", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -78,10 +82,12 @@ SIGNATURES = {
     "klf_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(_Filter), C.POINTER(C.c_void_p)]),
     "klf_retail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "klf_regroup": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_RegroupOpts), C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_result_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                     C.POINTER(_Counts)]),
     "klf_result_lines": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "klf_result_match_bits": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "klf_result_group_bits": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "klf_result_pattern_counts": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32,
                                             C.POINTER(C.c_uint32)]),
     "klf_result_last_unparsed": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -175,6 +181,7 @@ KLF_FILTER_STAGE_TIMES = 1
 KLF_FILTER_PATTERN_COUNTS = 2
 KLF_FILTER_FULL_INDEX = 4
 KLF_FILTER_NO_TIMING = 8
+KLF_REGROUP_INVERT = 1
 INDEX_MODES = {0: "full", 1: "windowed", 2: "on_demand"}  # klf_result_index_mode
 COMPACTIONS = {0: "gather", 1: "tiles", 2: "one_pass"}  # klf_result_compaction
 
@@ -312,6 +319,14 @@ class Result:
         _check(_lib.klf_result_match_bits(self._p, i, C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value) if n.value else b""
 
+    def group_bits(self, i: int) -> bytes:
+        """klf_result_group_bits: the bitmap the result was selected from, packed like
+        match_bits: G' after regroup (SPEC.md S4a), the match bitmap otherwise."""
+        p = C.c_void_p()
+        n = C.c_uint64()
+        _check(_lib.klf_result_group_bits(self._p, i, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
     def pattern_counts(self, i: int) -> List[int]:
         """klf_result_pattern_counts: matching lines of stream i per pattern (the run needs
         pattern_counts=True)."""
@@ -394,6 +409,19 @@ class Result:
         compaction only.  This result is stale afterwards (its output buffer is reused)."""
         r = C.c_void_p()
         _check(_lib.klf_retail(self._eng._h, self._p, int(tail), C.byref(r)), self._eng._h)
+        return Result(r.value or 0, self.n_streams, self._eng)
+
+    def regroup(self, before: int = 0, after: int = 0, invert: bool = False, tail: int = -1,
+                flags: Optional[int] = None) -> "Result":
+        """The same run with context lines and / or the match inverted (klf_regroup, SPEC.md
+        S4a: grep -B / -A / --invert-match), then --tail N: always from the run's own matches,
+        never from an earlier regroup.  This result is stale afterwards.  flags: the raw
+        KLF_REGROUP_* bits instead of `invert`."""
+        o = _RegroupOpts()
+        o.before, o.after = int(before), int(after)
+        o.flags = (KLF_REGROUP_INVERT if invert else 0) if flags is None else int(flags)
+        r = C.c_void_p()
+        _check(_lib.klf_regroup(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
         return Result(r.value or 0, self.n_streams, self._eng)
 
     def free(self):
