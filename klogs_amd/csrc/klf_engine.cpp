@@ -2507,7 +2507,9 @@ extern "C" int klf_debug_prefilter(const klf_pattern* pats, uint32_t n, const ui
     info[4] = cs.qf_anc_on ? 0x100u | cs.qf_anc_byte : 0u;
   }
   if (cs.mode != klf::CompiledSet::kGeneral || !cs.qf_on) return klf_debug_match(pats, n, content, len, match);
-  *match = klf::prefilter_match(cs, content, len, phase) ? 1 : 0;
+  // also_all: the engine's filter is kAll's (every parsed line); the other patterns' tables
+  // only serve the per-pattern counts
+  *match = (cs.also_all || klf::prefilter_match(cs, content, len, phase)) ? 1 : 0;
   return KLF_OK;
 }
 

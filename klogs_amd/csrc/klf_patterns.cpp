@@ -123,7 +123,16 @@ class Parser {
       bool flags_only = false;
       int a = atom(f, flags_only);
       if (a < 0 && !flags_only) return -1;
-      if (flags_only) continue;
+      if (flags_only) {
+        // Go's parser pushes nothing for a flag group or an empty \Q\E, so a repetition right
+        // after one takes the item before it (and starts a new one: `a*(?i)*` is (a*)*)
+        if (!items.empty() && at_repeat()) {
+          a = repeat(items.back());
+          if (a < 0) return -1;
+          items.back() = a;
+        }
+        continue;
+      }
       a = repeat(a);
       if (a < 0) return -1;
       items.push_back(a);
@@ -144,6 +153,7 @@ class Parser {
     long v = 0;
     while (j < n_ && p_[j] >= '0' && p_[j] <= '9') { v = std::min(v * 10 + (p_[j] - '0'), 100000L); ++j; }
     if (j == d0) return false;
+    if (j - d0 >= 2 && p_[d0] == '0') return false;  // Go parseInt: no leading zeros (`a{01}` is literal text)
     lo = (int)v;
     if (j < n_ && p_[j] == '}') { hi = lo; len = j + 1 - i_; return true; }
     if (j >= n_ || p_[j] != ',') return false;
@@ -152,9 +162,17 @@ class Parser {
     v = 0;
     while (j < n_ && p_[j] >= '0' && p_[j] <= '9') { v = std::min(v * 10 + (p_[j] - '0'), 100000L); ++j; }
     if (j >= n_ || p_[j] != '}') return false;
+    if (j - d1 >= 2 && p_[d1] == '0') return false;
     hi = (j == d1) ? -1 : (int)v;
     len = j + 1 - i_;
     return true;
+  }
+
+  bool at_repeat() const {
+    const int c = peek();
+    int lo, hi;
+    size_t len;
+    return c == '*' || c == '+' || c == '?' || (c == '{' && braces(lo, hi, len));
   }
 
   int repeat(int a) {
@@ -210,7 +228,7 @@ class Parser {
     }
     if (c == '^') { ++i_; return mk(RNode::kBot); }
     if (c == '$') { ++i_; return mk(RNode::kEot); }
-    if (c == '\\') return escape_atom(f);
+    if (c == '\\') return escape_atom(f, flags_only);
     ++i_;
     ByteSet s;
     s.set(c);
@@ -232,7 +250,7 @@ class Parser {
       } else {
         // flags: (?imsU-imsU) or (?imsU-imsU:...)
         size_t k = i_ + 1;
-        bool neg = false, saw = false, saw_neg_flag = false;
+        bool neg = false, saw_neg_flag = false;
         Flags nf = f;
         for (;; ++k) {
           if (k >= n_) return fail("missing closing )");
@@ -240,15 +258,13 @@ class Parser {
           if (ch == 'i' || ch == 'm' || ch == 's' || ch == 'U') {
             if (ch == 'i') nf.i = !neg;
             if (ch == 's') nf.s = !neg;
-            saw = true;
             if (neg) saw_neg_flag = true;
           } else if (ch == '-') {
             if (neg) return fail("invalid or unsupported Perl syntax");
             neg = true;
           } else if (ch == ':' || ch == ')') {
             if (neg && !saw_neg_flag) return fail("invalid or unsupported Perl syntax");
-            if (ch == ')' && !saw) return fail("invalid or unsupported Perl syntax");
-            break;
+            break;  // (no flag at all, `(?)`, is an empty flag group, as in Go's parsePerlFlags)
           } else {
             return fail("invalid or unsupported Perl syntax");
           }
@@ -321,7 +337,7 @@ class Parser {
     return false;
   }
 
-  int escape_atom(Flags& f) {
+  int escape_atom(Flags& f, bool& flags_only) {
     if (peek(1) == 'Q') {  // \Q...\E
       i_ += 2;
       std::vector<int> items;
@@ -332,7 +348,15 @@ class Parser {
         items.push_back(mkset(f.i ? fold(s) : s));
         ++i_;
       }
-      if (items.empty()) return mk(RNode::kEmpty);
+      if (items.empty()) {  // \Q\E is nothing at all (Go pushes no node)
+        flags_only = true;
+        return -1;
+      }
+      // the quoted text is one literal per byte: a repetition after \E takes the last byte
+      // (`\Qab\E+` is ab+), and a second one after it is a nested repetition
+      const int last = repeat(items.back());
+      if (last < 0) return -1;
+      items.back() = last;
       if (items.size() == 1) return items[0];
       int x = mk(RNode::kCat);
       pool[x].kids = items;
@@ -347,14 +371,15 @@ class Parser {
     return mkset(f.i ? fold(s) : s);
   }
 
-  bool posix_class(ByteSet& out) {
-    // at "[:"; returns false (no consumption) when not a known [:name:]
+  int posix_class(ByteSet& out) {
+    // at "[:"; Go's maybeParseNamedClass: the name runs to the next ":]" wherever it is;
+    // returns 0 (no consumption) when there is none, -1 for an unknown name
     size_t j = i_ + 2;
-    bool neg = false;
-    if (j < n_ && p_[j] == '^') { neg = true; ++j; }
     size_t k = j;
-    while (k < n_ && p_[k] >= 'a' && p_[k] <= 'z') ++k;
-    if (k + 1 >= n_ || p_[k] != ':' || p_[k + 1] != ']') return false;
+    while (k + 1 < n_ && !(p_[k] == ':' && p_[k + 1] == ']')) ++k;
+    if (k + 1 >= n_) return 0;
+    bool neg = false;
+    if (j < k && p_[j] == '^') { neg = true; ++j; }
     std::string name((const char*)p_ + j, k - j);
     ByteSet s;
     if (name == "alnum") s = range_set('0', '9') | range_set('A', 'Z') | range_set('a', 'z');
@@ -371,10 +396,10 @@ class Parser {
     else if (name == "upper") s = range_set('A', 'Z');
     else if (name == "word") s = perl_w();
     else if (name == "xdigit") s = range_set('0', '9') | range_set('A', 'F') | range_set('a', 'f');
-    else return false;
+    else { fail("invalid character class range"); return -1; }
     out |= neg ? ~s : s;
     i_ = k + 2;
-    return true;
+    return 1;
   }
 
   // class char: returns -2 on error, -3 when a set was added to `acc`, else the byte.
@@ -402,7 +427,11 @@ class Parser {
       if (c < 0) { fail("missing closing ]"); return false; }
       if (c == ']' && !first) { ++i_; break; }
       first = false;
-      if (c == '[' && peek(1) == ':' && posix_class(s)) continue;
+      if (c == '[' && peek(1) == ':') {
+        const int pc = posix_class(s);
+        if (pc < 0) return false;
+        if (pc) continue;
+      }
       int lo = class_char(s);
       if (lo == -2) return false;
       if (lo == -3) continue;
@@ -462,16 +491,19 @@ struct Builder {
     if (n.k == RNode::kRepeat) {
       int a = expand(n.kids[0]);
       std::vector<int> items;
-      for (int r = 0; r < n.lo; ++r) items.push_back(r == 0 ? a : clone(a));
       int used = n.lo;
       if (n.hi < 0) {
-        int st = (int)pool.size();
+        // x{n,} = x^(n-1) x+ : n copies, as count_pos counts them (x{0,} = x*: one copy)
+        for (int r = 0; r + 1 < n.lo; ++r) items.push_back(r == 0 ? a : clone(a));
         RNode s;
-        s.k = RNode::kStar;
-        s.kids = {used == 0 ? a : clone(a)};
+        s.k = n.lo == 0 ? RNode::kStar : RNode::kPlus;
+        s.kids = {n.lo <= 1 ? a : clone(a)};  // (the clone's nodes go in before the repetition's own)
         pool.push_back(s);
-        items.push_back(st);
-      } else if (n.hi > n.lo) {
+        items.push_back((int)pool.size() - 1);
+      } else {
+        for (int r = 0; r < n.lo; ++r) items.push_back(r == 0 ? a : clone(a));
+      }
+      if (n.hi > n.lo) {
         // x{lo,hi} = x^lo (x(x(...)?)?)?  — nested optionals keep it linear
         int tail = -1;
         for (int r = n.hi - n.lo - 1; r >= 0; --r) {
@@ -519,12 +551,16 @@ struct Builder {
   std::vector<uint64_t> follow;
   std::vector<ByteSet> pos_set;
   uint64_t a_bot = 0, a_eot = 0;
+  bool overflow = false;  // more than kMaxRegexPositions positions: the tables are void
 
   Info glushkov(int x) {
     const RNode& n = pool[x];
     switch (n.k) {
       case RNode::kEmpty: return {true, 0, 0};
       case RNode::kSet: case RNode::kBot: case RNode::kEot: {
+        // the tables are one u64 word per position set: a 65th position is refused here,
+        // whatever count_pos estimated before the expansion
+        if (npos >= kMaxRegexPositions) { overflow = true; return {false, 0, 0}; }
         int p = npos++;
         follow.push_back(0);
         pos_set.push_back(n.k == RNode::kSet ? n.set : ByteSet());
@@ -832,6 +868,11 @@ static bool build_glushkov(std::vector<RNode>& pool, int root, GlushkovTables& o
   }
   root = b.expand(root);
   Builder::Info info = b.glushkov(root);
+  if (b.overflow) {  // (count_pos equals the expansion's positions; this holds even if it ever does not)
+    err = "regex needs more than 64 Glushkov positions after {m,n} expansion";
+    err_code = KLF_ETOOBIG;
+    return false;
+  }
   out = GlushkovTables();
   out.npos = b.npos;
   out.follow = b.follow;

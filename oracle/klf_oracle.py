@@ -411,8 +411,8 @@ class _GoRegexToPy:
                 self.expect_close()
                 return "(?:" + inner + ")"
             m = re.match(rb"\?([imsU]*)(?:-([imsU]*))?(:|\))", self.p[self.i:])
-            if not m or (m.group(1) == b"" and m.group(2) is None and m.group(3) == b")") \
-                    or m.group(2) == b"":
+            # (Go's parsePerlFlags takes `(?)` as an empty flag group)
+            if not m or m.group(2) == b"":
                 raise PatternError("invalid or unsupported Perl syntax")
             newf = dict(flags)
             for ch in m.group(1).decode():
@@ -525,9 +525,10 @@ class _GoRegexToPy:
                 break
             first = False
             if c == 0x5B and self.peek(1) == 0x3A:  # [:name:]
-                m = re.match(rb"\[:(\^?)([a-z]+):\]", self.p[self.i:])
+                # Go maybeParseNamedClass: the name runs to the next ":]", wherever it is
+                m = re.match(rb"\[:(\^?)(.*?):\]", self.p[self.i:], re.S)
                 if m:
-                    if m.group(2).decode() not in _POSIX:
+                    if m.group(2).decode("latin-1") not in _POSIX:
                         raise PatternError("invalid character class range")
                     cls = _POSIX[m.group(2).decode()]
                     if flags["i"]:  # appendGroup: fold the group, then negate it

@@ -101,7 +101,8 @@ RX = [rb"a.c", rb"^abc", rb"abc$", rb"(?i)error", rb"err(?i:OR)", rb"\d{3}-\d{4}
       rb"a{,2}", rb"a|b|", rb"x*y", rb"^$", rb"^", rb"$", rb"\Qa.b\E", rb"[^a]", rb"\x41", rb"(?:ab)+c",
       rb"user=\w+ took \d+ms", rb"(a|ab)(c|bcd)(d*)", rb"(^|x)y", rb"y($|x)", rb"a^b", rb"a$b", rb"(?:^)*a",
       rb"(a*)*b", rb"[a-c]{2,4}d?", rb"(?s).", rb"\.\*\+", rb"[\d\s]+x", rb"(?i)[a-f]{3}", rb"a?b?c?$",
-      rb"((a|b)*c){2}", rb"\A[0-9]+\z", rb"(?m)^x$", rb"status=(200|404|5\d\d)", rb"[]a]+", rb"[a-]+z"]
+      rb"((a|b)*c){2}", rb"\A[0-9]+\z", rb"(?m)^x$", rb"status=(200|404|5\d\d)", rb"[]a]+", rb"[a-]+z",
+      rb"x{1,}ab", rb"^x{2,}$", rb"(?:ab){2,}c", rb"\d{3,}ms", rb"a{01}"]
 ALPH = b"abcdxyzABCERO0123456789-= .*+\tq"
 
 
@@ -114,6 +115,7 @@ def test_glushkov_tables_vs_python_re(pat):
     rng = random.Random(hash(pat) & 0xFFFF)
     ref = po.Pattern("regex", pat)
     samples = [b"", b"a", b"abc", b"xabc", b"ERROR", b"555-1234", b"acd", b"abcd", b"y", b"xy", b"a.b", b"x"]
+    samples += [b"xab", b"ab", b"xx", b"xxx", b"ababc", b"abc", b"123ms", b"12ms", b"a{01}"]  # exact minimum counts
     samples += [_rand_text(rng, rng.randint(0, 12)) for _ in range(300)]
     for s in samples:
         assert E.debug_match(s, match=[pat]) == ref.matches(s), (pat, s)
@@ -136,6 +138,7 @@ def test_mixed_literals_and_regexes():
     for _ in range(300):
         s = _rand_text(rng, rng.randint(0, 40))
         if rng.random() < 0.2:
-            s += rng.choice([b"user=bob took 1234ms", b"panic: x", b"ERR_CONN_RESET"])
+            s += rng.choice([b"user=bob took 1234ms", b"user=bob took 123ms", b"user=bob took 12ms", b"panic: x",
+                             b"ERR_CONN_RESET"])
         want = any(l in s for l in lits) or any(po.Pattern("regex", p).matches(s) for p in pats)
         assert E.debug_match(s, grep=lits, match=pats) == want, s
