@@ -186,6 +186,44 @@ typedef struct klf_regroup_opts {
 } klf_regroup_opts;
 int klf_regroup(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out);
 
+/* A time window over the latest run (SPEC.md S4b; --from / --until): with G' as klf_regroup
+ * builds it from before / after / flags (G' = M when all are 0; on an engine without patterns
+ * G' = the parsed lines), the selection becomes G'' = the lines of G' whose instant ts lies in
+ * [from, until): from <= ts < until, compared as klf_time is (sec, then nsec).  Context is
+ * taken from all of M first and cut by the window afterwards: a context line outside the
+ * window is dropped, a match outside it still lends context to lines inside.  --since and the
+ * tail rule with `tail` then run over G'' as they ran over M, so `until` with tail = 100 is
+ * the last 100 selected lines before `until`; `from` differs from since in that it applies
+ * before the tail count.  An unparseable line has no instant and is never in G'': on an
+ * engine without patterns a window open on both sides equals the plain run only where every
+ * line parses.  counts.matched = |G''|; lines / parsed / since_ok do not change.
+ * from.sec = KLF_TIME_MIN_SEC is open below, until.sec = KLF_TIME_MAX_SEC open above;
+ * from >= until is an empty window (legal, empty output).  Timestamps need not ascend: every
+ * line is decided on its own.  With both bounds open and no context the call is
+ * klf_retail(prev, tail) over M byte for byte on an engine with patterns.
+ * The contract is klf_retail's: prev must be the engine's latest result (KLF_ESTATE) and is
+ * stale afterwards.  Beside the bitmap and the line meta, each line of G' costs its line-index
+ * entry and one read of the first 32 bytes of the line in the batch, which must still be
+ * resident (klf_run_device: the caller's buffer); the batch is never scanned again.  A window
+ * always starts from M: it never compounds with an earlier window or regroup; a klf_retail of
+ * the new result re-tails over G''; a klf_regroup of it starts from M with no window; the next
+ * klf_run / klf_run_device is untouched.  klf_result_group_bits returns G'' on the new result
+ * and on a klf_retail of it, also on an engine without patterns.  KLF_EINVAL: a null argument,
+ * tail < -1, unknown flag bits, a non-zero _reserved (also a klf_time's), nsec outside
+ * [0, 1e9), non-zero before / after / flags on an engine without patterns (context needs a
+ * pattern).  Replaces nothing in the reference (kubelet knows sinceTime only, a lower bound:
+ * getLopOpts, cmd/root.go:201-221).  Out of scope: follow sessions and shard.run_split, as
+ * for klf_regroup. */
+#define KLF_TIME_MIN_SEC INT64_MIN /* from.sec: open below  */
+#define KLF_TIME_MAX_SEC INT64_MAX /* until.sec: open above */
+typedef struct klf_window_opts {
+  klf_time from, until;   /* [from, until) */
+  uint32_t before, after; /* context, as klf_regroup_opts */
+  uint32_t flags;         /* KLF_REGROUP_INVERT, 0 = none */
+  uint32_t _reserved;     /* 0 */
+} klf_window_opts;        /* 48 bytes */
+int klf_window(klf_engine* e, klf_result* prev, const klf_window_opts* o, int64_t tail, klf_result** out);
+
 /* ---- results -------------------------------------------------------------------- */
 /* Selected bytes of one stream (host view, D2H on first access; bytes == NULL: len and
  * counts only, no D2H). */
@@ -202,7 +240,9 @@ int klf_result_match_bits(klf_result* r, uint32_t stream_id, const uint8_t** bit
                           uint64_t* nbytes);
 /* Selection bitmap of one stream, packed like klf_result_match_bits: G' on a result of
  * klf_regroup (and on a klf_retail of one), M on every other result (klf_result_match_bits
- * returns M on all of them).  KLF_EINVAL when the engine has no patterns. */
+ * returns M on all of them); G'' on a result of klf_window that cut or regrouped (and on a
+ * klf_retail of one).  KLF_EINVAL when the engine has no patterns, except on a klf_window
+ * result (and a klf_retail of one): there it is G'', a subset of the parsed lines. */
 int klf_result_group_bits(klf_result* r, uint32_t stream_id, const uint8_t** bits,
                           uint64_t* nbytes);
 /* Per-pattern match counts of one stream (SURVEY.md §8a K4/K5 `count[stream][pattern]`, the

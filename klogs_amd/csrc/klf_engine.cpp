@@ -1758,10 +1758,15 @@ extern "C" int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n,
 
 static int ensure_index(klf_engine* e);
 
-// klf_retail (o null: over the bitmap the latest result was selected from) and klf_regroup
-// (o: over G', built first from the run's match bitmap in d_bits).
+// klf_retail (o null: over the bitmap the latest result was selected from), klf_regroup
+// (o: over G', built first from the run's match bitmap in d_bits) and klf_window (o and tw:
+// G' only when o asks for context or inversion, then cut by the time window when a bound is
+// closed or the engine has no patterns; always from M).
+static bool window_closed(const klf_window_opts* tw) {
+  return tw->from.sec != KLF_TIME_MIN_SEC || tw->until.sec != KLF_TIME_MAX_SEC;
+}
 static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
-                       const char* what) {
+                       const char* what, const klf_window_opts* tw = nullptr) {
   if (prev->gen != e->gen || e->last_gen != prev->gen)
     return set_err(e, KLF_ESTATE, std::string(what) + ": not the latest run");
   if (int rc = ensure_index(e)) return rc;
@@ -1773,7 +1778,11 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
   r->seg_of = prev->seg_of;
   r->seg_base = prev->seg_base;
   r->has_bits = prev->has_bits;
-  r->grouped = o ? true : prev->grouped;
+  // (a window without patterns selects over the parsed lines: the tail stage then runs in
+  // bitmap mode, over d_gbits, like a regrouped result)
+  const bool regroup = o && (!tw || o->before || o->after || o->flags);
+  const bool cut = tw && (window_closed(tw) || !prev->has_bits);
+  r->grouped = (o || tw) ? (regroup || cut) : prev->grouped;
   r->total_lines = prev->total_lines;
   r->counted = prev->counted;
   r->pcount_ok = prev->pcount_ok;
@@ -1792,7 +1801,9 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
     uint32_t rmask = 0;
     hipError_t h = hipSuccess;
     klf::RegroupArgs g{};
-    if (o) {  // always from M: regroups do not compound
+    klf::WindowArgs wa{};
+    if (o || tw) a.bits = e->d_bits.as<uint32_t>();  // always from M: regroups and windows do not compound
+    if (regroup) {
       const uint64_t nw = a.cap_lines / 32 + 1, nc = a.cap_lines / klf::kMatchChunk + 1;
       h = e->d_gbits.ensure(nw * 4);
       if (h == hipSuccess) h = e->d_gsum.ensure(nc * 4 * 8);
@@ -1809,7 +1820,29 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
       g.nchunks = (prev->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;  // (<= nc: lines <= cap_lines)
       a.bits = g.bits_out;
     }
-    if (h == hipSuccess) h = klf::launch_retail(a, st, e->ev, e->num_cus, &rmask, o ? &g : nullptr);
+    if (cut) {
+      if (h == hipSuccess) h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
+      wa.bits_in = prev->has_bits ? a.bits : nullptr;  // G' (d_gbits, in place), M, or the parsed lines
+      wa.bits_out = e->d_gbits.as<uint32_t>();
+      wa.meta = a.meta;
+      wa.line_off = a.line_off;
+      wa.bytes = a.bytes;
+      wa.segs = a.segs;
+      wa.segout = a.segout;
+      wa.nsegs = nsegs;
+      wa.cap_lines = a.cap_lines;
+      wa.nchunks = (prev->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
+      wa.from_sec = tw->from.sec;
+      wa.from_nsec = tw->from.nsec;
+      wa.until_sec = tw->until.sec;
+      wa.until_nsec = tw->until.nsec;
+      since_digits(tw->from.sec, tw->from.nsec, wa.from_dig);
+      since_digits(tw->until.sec, tw->until.nsec, wa.until_dig);
+      a.bits = wa.bits_out;
+      a.grep_mode = prev->has_bits ? a.grep_mode : (uint32_t)klf::kGrepGeneral;  // (a.pats stays empty: unread)
+    }
+    if (h == hipSuccess)
+      h = klf::launch_retail(a, st, e->ev, e->num_cus, &rmask, regroup ? &g : nullptr, cut ? &wa : nullptr);
     uint32_t short_out = 0;
     if (h == hipSuccess) h = e->h_rb.ensure(kCtrBytes + nsegs * sizeof(SegOut));
     if (h == hipSuccess)
@@ -1856,6 +1889,19 @@ extern "C" int klf_regroup(klf_engine* e, klf_result* prev, const klf_regroup_op
     return set_err(e, KLF_EINVAL, "klf_regroup: unknown flag bits or a non-zero _reserved");
   if (!prev->has_bits) return set_err(e, KLF_EINVAL, "klf_regroup: the engine has no patterns");
   return retail_impl(e, prev, o, tail, out, "klf_regroup");
+}
+
+extern "C" int klf_window(klf_engine* e, klf_result* prev, const klf_window_opts* o, int64_t tail, klf_result** out) {
+  if (!e || !prev || !o || !out || prev->e != e || tail < -1) return KLF_EINVAL;
+  *out = nullptr;
+  if ((o->flags & ~KLF_REGROUP_INVERT) || o->_reserved || o->from._reserved || o->until._reserved)
+    return set_err(e, KLF_EINVAL, "klf_window: unknown flag bits or a non-zero _reserved");
+  if (o->from.nsec < 0 || o->from.nsec >= 1000000000 || o->until.nsec < 0 || o->until.nsec >= 1000000000)
+    return set_err(e, KLF_EINVAL, "klf_window: nsec outside [0, 1e9)");
+  if (!prev->has_bits && (o->before || o->after || o->flags))
+    return set_err(e, KLF_EINVAL, "klf_window: context and inversion need a pattern");
+  const klf_regroup_opts g{o->before, o->after, o->flags, 0};
+  return retail_impl(e, prev, &g, tail, out, "klf_window", o);
 }
 
 extern "C" int klf_run(klf_engine* e, const klf_filter* f, klf_result** out) {
@@ -1932,7 +1978,7 @@ static void fill_counts(const klf_result* r, int64_t s, const uint64_t len, klf_
   c->lines = so.line_hi - so.line_lo;
   c->parsed = so.parsed;
   c->since_ok = so.since_ok;
-  c->matched = mode == klf::CompiledSet::kNone ? c->lines : so.matched;
+  c->matched = mode == klf::CompiledSet::kNone && !r->grouped ? c->lines : so.matched;  // (grouped: |G''|)
   c->selected = so.sel_hi - so.sel_lo;
   c->out_bytes = len;
 }
@@ -2163,7 +2209,7 @@ extern "C" int klf_result_lines(klf_result* r, uint32_t id, const uint64_t** off
 static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes, int which) {
   int rc = check_result(r, id);
   if (rc) return rc;
-  if (!r->has_bits) return KLF_EINVAL;
+  if (!r->has_bits && !(which && r->grouped)) return KLF_EINVAL;  // (no patterns: a window's G'' only)
   klf_engine* e = r->e;
   auto& hb = r->hbits[which];
   if (!hb.have) {

@@ -2990,6 +2990,108 @@ __global__ __launch_bounds__(256) void k_rg_build(RegroupArgs g) {
   }
 }
 
+// ================================================= time window (klf_window, SPEC.md S4b) ==
+// G'' = the lines of G' whose instant lies in [from, until).  One block per kMatchChunk
+// lines, one thread per bitmap word, like k_rg_build; a wave whose 64 words of G' are zero
+// costs their loads only.  A line of G' costs its index entry and the first 32 bytes of the line in the batch
+// (every line of G' is parsed: its prefix ends at its first space, inside the line).
+// Timestamps need not ascend, so every line is decided on its own.
+//
+// The canonical kubelet prefix is decided as the scan's parse_fast decides since: the same
+// shape test and big-endian digit packing, then two lexicographic compares against the
+// bounds' digits (WindowArgs::from_dig / until_dig, clamped to the fast path's years
+// 1970..2099 by the host).  The line is parsed already, so its date is valid and the field
+// range checks are not repeated.  Every other shape goes to the general parser.
+__device__ __forceinline__ bool dig_ge(const uint32_t (&p)[6], const uint32_t (&c)[6]) {
+  const uint64_t a0 = (uint64_t)p[0] << 32 | p[1], a1 = (uint64_t)p[2] << 32 | p[3], a2 = (uint64_t)p[4] << 32 | p[5];
+  const uint64_t c0 = (uint64_t)c[0] << 32 | c[1], c1 = (uint64_t)c[2] << 32 | c[3], c2 = (uint64_t)c[4] << 32 | c[5];
+  return a0 > c0 || (a0 == c0 && (a1 > c1 || (a1 == c1 && a2 >= c2)));
+}
+__device__ __forceinline__ bool tw_line_in(const WindowArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
+                                           uint64_t seg_len) {
+  // two unaligned 16-B global loads at the line start (inside the allocation: kAllocSlack)
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 x0, x1;
+  __builtin_memcpy(&x0, segp + off, 16);
+  __builtin_memcpy(&x1, segp + off + 16, 16);
+  const uint32_t w[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+  // separators: '-' 4, '-' 7, 'T' 10, ':' 13, ':' 16, '.' 19, 'Z' 29, ' ' 30
+  const uint32_t sep = ((w[1] ^ 0x2D00002Du) & 0xFF0000FFu) | ((w[2] ^ 0x00540000u) & 0x00FF0000u) |
+                       ((w[3] ^ 0x00003A00u) & 0x0000FF00u) | ((w[4] ^ 0x2E00003Au) & 0xFF0000FFu) |
+                       ((w[7] ^ 0x00205A00u) & 0x00FFFF00u);
+  const uint32_t p[6] = {__builtin_amdgcn_perm(0u, w[0], 0x00010203u),                   // Y Y Y Y
+                         __builtin_amdgcn_perm(w[2], w[1], 0x01020405u),                 // M M D D
+                         __builtin_amdgcn_perm(w[3], w[2], 0x03040607u),                 // h h m m
+                         __builtin_amdgcn_perm(w[5], w[4], 0x01020405u),                 // s s n0 n1
+                         __builtin_amdgcn_perm(w[6], w[5], 0x02030405u),                 // n2 n3 n4 n5
+                         __builtin_amdgcn_perm(w[7], w[6], 0x02030C04u) | 0x00003000u};  // n6 n7 0 n8
+  const uint32_t hi = ((p[0] ^ 0x30303030u) | (p[1] ^ 0x30303030u) | (p[2] ^ 0x30303030u) | (p[3] ^ 0x30303030u) |
+                       (p[4] ^ 0x30303030u) | (p[5] ^ 0x30303030u)) & 0xF0F0F0F0u;
+  const uint32_t lo = ((p[0] + 0x06060606u) | (p[1] + 0x06060606u) | (p[2] + 0x06060606u) | (p[3] + 0x06060606u) |
+                       (p[4] + 0x06060606u) | (p[5] + 0x06060606u)) & 0x40404040u;
+  if ((sep | hi | lo) == 0u && p[0] - 0x31393730u <= 0x32303939u - 0x31393730u)  // canonical, year 1970..2099
+    return dig_ge(p, g.from_dig) && !dig_ge(p, g.until_dig);
+  TsResult r;
+  uint32_t plen;
+  if (!parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) return false;
+  return !time_before(r.sec, r.nsec, g.from_sec, g.from_nsec) && time_before(r.sec, r.nsec, g.until_sec, g.until_nsec);
+}
+
+// The n-th (0-based) set bit of w, n < popcount(w): a binary search on popcounts.
+__device__ __forceinline__ uint32_t nth_set_bit(uint32_t w, uint32_t n) {
+  uint32_t pos = 0;
+#pragma unroll
+  for (uint32_t width = 16; width >= 1; width >>= 1) {
+    const uint32_t c = (uint32_t)__popc((w >> pos) & ((1u << width) - 1u));
+    if (n >= c) { n -= c; pos += width; }
+  }
+  return pos;
+}
+
+// A wave shares the lines of its 64 words over its lanes (LDS: the words, the exclusive
+// prefix of their popcounts, each word's first stream): lane i of round r takes the wave's
+// (64 r + i)-th line of G', so a round reads 64 consecutive lines of G' -- consecutive index
+// entries and, where G' is dense, neighbouring bytes of the batch.  One thread per word walking
+// its own 32 lines took 2.13 ms on the C3 shape (55.6 M lines, all in G'); see DESIGN.md.
+__global__ __launch_bounds__(256) void k_tw_build(WindowArgs g) {
+  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64], s_out[4][64];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
+  const uint64_t nw = g.cap_lines / 32 + 1;  // words of the bitmaps
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    uint32_t in = 0;
+    if (l0 < L) in = g.bits_in ? g.bits_in[w] & word_range_mask(w, 0, L) : parsed_word(g.meta, w, L);
+    const uint32_t cnt = (uint32_t)__popc(in);
+    const uint32_t incl = wave_incl_scan_add(cnt, lane);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of G'
+    __syncthreads();  // (the previous chunk's s_out is read)
+    s_in[wv][lane] = in;
+    s_pre[wv][lane] = incl - cnt;
+    s_seg[wv][lane] = in ? find_seg_by_line(g.segout, g.nsegs, l0) : 0u;
+    s_out[wv][lane] = 0u;
+    __syncthreads();
+    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
+    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
+      const uint32_t k = k0 + (uint32_t)lane;
+      if (k < total) {
+        uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
+#pragma unroll
+        for (uint32_t step = 32; step >= 1; step >>= 1)
+          if (s_pre[wv][j + step] <= k) j += step;
+        const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
+        const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
+        uint32_t s = s_seg[wv][j];
+        while (l >= g.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
+        const SegDesc sd = g.segs[s];
+        if (tw_line_in(g, g.bytes + sd.base, g.line_off[l + s], sd.len)) atomicOr(&s_out[wv][j], 1u << b);
+      }
+    }
+    __syncthreads();
+    if (w < nw) g.bits_out[w] = s_out[wv][lane];
+  }
+}
+
 // Zeroes the run's counters and per-stream records (one launch instead of memsets).
 __global__ __launch_bounds__(256) void k_init(RunArgs a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -4801,7 +4903,7 @@ hipError_t launch_tcopy(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int nu
 }
 
 hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int num_cus, uint32_t* ev_mask,
-                         const RegroupArgs* g) {
+                         const RegroupArgs* g, const WindowArgs* tw) {
   uint32_t m_local = 0;
   uint32_t& m = ev_mask ? *ev_mask : m_local;
   hipError_t e = hipEventRecord(ev[0], st);
@@ -4815,6 +4917,11 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
     hipLaunchKernelGGL(k_rg_carry, dim3(1), dim3(256), 0, st, *g);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_rg_build, dim3(gc), dim3(256), 0, st, *g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (tw && tw->nchunks) {  // then the time window (a.bits = tw->bits_out)
+    const uint64_t gmax = (uint64_t)num_cus * 16;
+    hipLaunchKernelGGL(k_tw_build, dim3((uint32_t)(tw->nchunks < gmax ? tw->nchunks : gmax)), dim3(256), 0, st, *tw);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_retail_init, dim3((a.nsegs + 255) / 256 < 1024 ? (a.nsegs + 255) / 256 : 1024), dim3(256), 0,

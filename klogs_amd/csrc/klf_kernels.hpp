@@ -381,6 +381,26 @@ struct RegroupArgs {
   uint64_t nchunks;
 };
 
+// Time window over a finished run (klf_window, SPEC.md S4b): k_tw_build reads a selection
+// bitmap G' and, for each of its lines, the first 32 bytes of the line in the resident batch,
+// and writes G'' = the lines of G' whose instant lies in [from, until).
+struct WindowArgs {
+  const uint32_t* bits_in;  // G', [cap_lines / 32 + 1]; null: the parsed lines (no patterns).
+                            // May be bits_out (a thread reads its word before it writes it)
+  uint32_t* bits_out;       // G'', same layout
+  const uint16_t* meta;     // [cap_lines]
+  const uint64_t* line_off; // [cap_lines + nsegs] the run's line index
+  const uint8_t* bytes;     // the batch
+  const SegDesc* segs;      // [nsegs]
+  const SegOut* segout;     // [nsegs]
+  uint32_t nsegs;
+  uint64_t cap_lines;
+  uint64_t nchunks;         // kMatchChunk chunks holding lines
+  int64_t from_sec, until_sec;
+  int32_t from_nsec, until_nsec;
+  uint32_t from_dig[6], until_dig[6];  // the bounds packed like RunArgs::since_dig
+};
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]
@@ -398,8 +418,10 @@ hipError_t launch_pipeline(const RunArgs& a, hipStream_t stream, hipEvent_t* ev,
 // Re-runs matched counts, tail and compaction of the last pipeline with a.tail changed.
 // g (nullable): first builds the selection bitmap g->bits_out (= a.bits) from g->bits_in
 // (k_rg_sum / k_rg_carry / k_rg_build), inside the same ev[0] .. ev[5] bracket.
+// tw (nullable): then cuts it by a time window (k_tw_build; tw->bits_out = a.bits), same bracket.
 hipError_t launch_retail(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus,
-                         uint32_t* ev_mask = nullptr, const RegroupArgs* g = nullptr);
+                         uint32_t* ev_mask = nullptr, const RegroupArgs* g = nullptr,
+                         const WindowArgs* tw = nullptr);
 // Data statistics (kGramHistWords u32, zeroed here) of the first `sample` bytes of each of
 // up to 16 segments: byte counts, and the 2-grams at even offsets (folded like the
 // prefilter's grams).

@@ -2,12 +2,17 @@
 // over captured log bodies, with the filter on the GPU through libklf.
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
-//                [-A N] [-B N] [-C N] [--invert-match]
+//                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
 //
 // -A / -B / -C N (lines of context after / before / around a matching line) and
 // --invert-match (the lines that do not match) need a --grep or --match; they are grep's,
 // not the reference's (-v stays its version flag): SPEC.md S4a, klf_regroup.
+//
+// --from X / --until X keep the lines whose timestamp lies in [from, until) (SPEC.md S4b,
+// klf_window), before --since and --tail apply: X is an RFC3339Nano instant or a Go duration
+// meaning that long before --now.  They work with and without a pattern and combine with the
+// context flags in one call.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -59,6 +64,8 @@ void usage() {
                "usage: klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...\n"
                "                    [-A N] [-B N] [-C N] [--invert-match]   (with --grep / --match: lines of\n"
                "                    context after / before / around a match; the lines that do not match)\n"
+               "                    [--from X] [--until X]   (the lines with from <= timestamp < until, before\n"
+               "                    --since / --tail apply; X: an RFC3339Nano instant, or a duration before --now)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -74,6 +81,8 @@ int main(int argc, char** argv) {
   std::vector<std::string> greps, matches;
   klf_regroup_opts regroup{0, 0, 0, 0};
   bool regrouped = false;  // any of -A / -B / -C / --invert-match
+  std::string from_arg, until_arg;
+  bool from_set = false, until_set = false;  // --from / --until
   auto context = [&](const std::string& v) -> uint32_t {
     char* end = nullptr;
     const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
@@ -97,6 +106,8 @@ int main(int argc, char** argv) {
     else if (a == "-B" || a == "--before-context") regroup.before = context(val());
     else if (a == "-C" || a == "--context") regroup.before = regroup.after = context(val());
     else if (a == "--invert-match") { regroup.flags |= KLF_REGROUP_INVERT; regrouped = true; }
+    else if (a == "--from") { from_arg = val(); from_set = true; }
+    else if (a == "--until") { until_arg = val(); until_set = true; }
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -113,6 +124,22 @@ int main(int argc, char** argv) {
   }
   if (manifest.empty()) usage();
   if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
+  // --from / --until: an instant, or a duration before `now` (--now may follow them)
+  klf_window_opts window{{KLF_TIME_MIN_SEC, 0, 0}, {KLF_TIME_MAX_SEC, 0, 0},
+                         regroup.before, regroup.after, regroup.flags, 0};
+  auto bound = [&](const std::string& v, klf_time* t) {
+    if (klf_parse_rfc3339nano((const uint8_t*)v.data(), v.size(), t) == 0) return;
+    int64_t ns = 0;
+    char perr[256];
+    if (klh_parse_duration(v.c_str(), &ns, perr, sizeof(perr)) != KLH_OK) usage();
+    int64_t sec = now.sec - ns / 1000000000, nsec = (int64_t)now.nsec - ns % 1000000000;
+    if (nsec < 0) { nsec += 1000000000; --sec; }
+    if (nsec >= 1000000000) { nsec -= 1000000000; ++sec; }
+    *t = klf_time{sec, (int32_t)nsec, 0};
+  };
+  if (from_set) bound(from_arg, &window.from);
+  if (until_set) bound(until_arg, &window.until);
+  const bool windowed = from_set || until_set;
   if (logpath.empty()) {  // defaultLogPath (:47)
     char buf[128];
     klh_default_log_path(now.sec, buf, sizeof(buf));
@@ -218,10 +245,16 @@ int main(int argc, char** argv) {
     // context / inversion: the run itself with --tail 0 (the cheapest run that leaves the
     // line index and the match bitmap behind), then klf_regroup applies the user's tail
     const int64_t user_tail = filter.tail;
-    if (regrouped) filter.tail = 0;
+    if (regrouped || windowed) filter.tail = 0;
     rc = klf_run(e, &filter, &r);
     if (rc != KLF_OK) panic_exit(std::string("klf_run: ") + klf_strerror(rc) + ": " + klf_last_error(e));
-    if (regrouped) {
+    if (windowed) {  // (with the context flags, if any, in the one call)
+      klf_result* g = nullptr;
+      rc = klf_window(e, r, &window, user_tail, &g);
+      if (rc != KLF_OK) panic_exit(std::string("klf_window: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      klf_result_free(r);
+      r = g;
+    } else if (regrouped) {
       klf_result* g = nullptr;
       rc = klf_regroup(e, r, &regroup, user_tail, &g);
       if (rc != KLF_OK) panic_exit(std::string("klf_regroup: ") + klf_strerror(rc) + ": " + klf_last_error(e));

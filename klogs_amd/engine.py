@@ -28,6 +28,8 @@ KLF_EIO = -7
 KLF_PAT_LITERAL = 0
 KLF_PAT_REGEX = 1
 GO_ZERO_TIME = (-62135596800, 0)
+TIME_MIN_SEC = -(1 << 63)     # KLF_TIME_MIN_SEC: klf_window_opts.from.sec, open below
+TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, open above
 
 MODE_NAMES = {0: "none", 1: "never", 2: "all", 3: "literal1", 4: "general"}
 
@@ -59,6 +61,11 @@ class _RegroupOpts(C.Structure):
     _fields_ = [("before", C.c_uint32), ("after", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class _WindowOpts(C.Structure):
+    _fields_ = [("from_", _Time), ("until", _Time), ("before", C.c_uint32), ("after", C.c_uint32),
+                ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
 class _Counts(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("parsed", C.c_uint64), ("since_ok", C.c_uint64),
                 ("matched", C.c_uint64), ("selected", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -83,6 +90,7 @@ SIGNATURES = {
                                  C.POINTER(C.c_uint64), C.POINTER(_Filter), C.POINTER(C.c_void_p)]),
     "klf_retail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_regroup": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_RegroupOpts), C.c_int64, C.POINTER(C.c_void_p)]),
+    "klf_window": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_WindowOpts), C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_result_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                     C.POINTER(_Counts)]),
     "klf_result_lines": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -422,6 +430,24 @@ class Result:
         o.flags = (KLF_REGROUP_INVERT if invert else 0) if flags is None else int(flags)
         r = C.c_void_p()
         _check(_lib.klf_regroup(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
+        return Result(r.value or 0, self.n_streams, self._eng)
+
+    def window(self, from_: Optional[Tuple[int, int]] = None, until: Optional[Tuple[int, int]] = None,
+               before: int = 0, after: int = 0, invert: bool = False, tail: int = -1,
+               flags: Optional[int] = None) -> "Result":
+        """The same run cut to the instants [from_, until) (klf_window, SPEC.md S4b), after the
+        context / inversion of `regroup` and before --since and --tail N.  Bounds are
+        (sec, nsec) tuples, None = open.  Always from the run's own matches (without patterns:
+        its parsed lines).  This result is stale afterwards."""
+        o = _WindowOpts()
+        lo = (TIME_MIN_SEC, 0) if from_ is None else from_
+        hi = (TIME_MAX_SEC, 0) if until is None else until
+        o.from_.sec, o.from_.nsec = int(lo[0]), int(lo[1])
+        o.until.sec, o.until.nsec = int(hi[0]), int(hi[1])
+        o.before, o.after = int(before), int(after)
+        o.flags = (KLF_REGROUP_INVERT if invert else 0) if flags is None else int(flags)
+        r = C.c_void_p()
+        _check(_lib.klf_window(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
         return Result(r.value or 0, self.n_streams, self._eng)
 
     def free(self):

@@ -1,10 +1,18 @@
 #!/usr/bin/env python3
 """Runs one BASELINE config's device-resident filter a few times (profiling driver).
 
-    python scripts/run_config.py c1|c2|c3|c4|c5 [--steps K] [--warmup W]
+    python scripts/run_config.py c1|c2|c3|c4|c5 [--steps K] [--warmup W] [--window FRAC]
 
 bench.run_config without the checks, the CPU baseline, the write and capture paths.
-Prints the result dict as one JSON line."""
+Prints the result dict as one JSON line.
+
+--window FRAC measures klf_window instead (SPEC.md S4b, DESIGN.md "Time window"): per timed
+step one run of the config (its patterns and --tail, no --since), then a window over the middle
+FRAC of the streams' time span with the same --tail, then a fresh run over the same resident
+batch with since = the window's lower bound (the nearest thing the engine could do before
+klf_window).  Reports the medians of
+klf_result_timing[4] of the three, and the wall time of the klf_window call (it includes the
+line index a run without patterns and without --tail left out, built on first use)."""
 import argparse
 import json
 import sys
@@ -16,18 +24,68 @@ sys.path.insert(0, str(ROOT))
 import bench  # noqa: E402
 
 
+def window_probe(name: str, frac: float, steps: int, warmup: int, now: int) -> dict:
+    import time
+
+    import numpy as np
+    import torch
+    from klogs_amd import engine as E
+    from klogs_amd import synth
+
+    sizes, kind, pats, permille, mode, desc = bench.config_table(name)
+    dev, seg_base, lens = bench.load_batch(sizes, kind, permille, list(range(len(sizes))), 0)
+    tail = -1 if mode == "-l" else bench.TAIL
+    since = None  # (the window stands in for the config's --since 5m, which would drop all it selects)
+    lo = synth.T0 + int(synth.SPAN * (0.5 - frac / 2))
+    frm, until = (lo, 0), (lo + int(synth.SPAN * frac), 0)
+    eng = E.Engine(0, hip_stream=torch.cuda.current_stream().cuda_stream, **pats)
+    ptr = dev.data_ptr()
+    run_ms, win_ms, rerun_ms, wall_ms = [], [], [], []
+    counts = {}
+    for i in range(warmup + steps):
+        r = eng.run_device(ptr, seg_base, lens, since=since, tail=tail)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        w = r.window(frm, until, tail=tail)  # (returns after its counts came back: synchronous)
+        t_wall = (time.perf_counter() - t0) * 1e3
+        t_run, t_win = r.timing()[4], w.timing()[4]
+        counts = {"window": w.totals()}
+        r.free()
+        w.free()
+        r2 = eng.run_device(ptr, seg_base, lens, since=frm, tail=tail)
+        t_rerun = r2.timing()[4]
+        counts["rerun"] = r2.totals()
+        r2.free()
+        if i >= warmup:
+            run_ms.append(t_run)
+            win_ms.append(t_win)
+            rerun_ms.append(t_rerun)
+            wall_ms.append(t_wall)
+    med = lambda v: round(float(np.median(v)), 4)
+    return {"workload": desc, "streams": len(lens), "bytes": int(sum(lens)), "window_frac": frac, "steps": steps,
+            "from": frm[0], "until": until[0], "tail": tail,
+            "run_device_ms": med(run_ms), "window_ms": med(win_ms), "window_call_wall_ms": med(wall_ms), "rerun_since_from_ms": med(rerun_ms),
+            "window_ms_all": [round(x, 4) for x in win_ms], "rerun_ms_all": [round(x, 4) for x in rerun_ms],
+            "counts": counts}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--probe", action="store_true", help="add bench.box_probe (the box's copy / read rates)")
+    ap.add_argument("--window", type=float, default=None, metavar="FRAC",
+                    help="time klf_window over the middle FRAC of the time span against a rerun with since = from")
     a = ap.parse_args()
     ns = argparse.Namespace(steps=a.steps, warmup=a.warmup, no_verify=True, no_write=True, no_capture=True,
                             no_cpu_baseline=True, capture_piece=4 << 20, full=True, dump_outputs=None)
     now = bench.synth.T0 + bench.synth.SPAN + 1
     probe = bench.box_probe(0) if a.probe else None
-    out = bench.run_config(a.config, ns, 0, now)
+    if a.window is not None:
+        out = window_probe(a.config, a.window, a.steps, a.warmup, now)
+    else:
+        out = bench.run_config(a.config, ns, 0, now)
     if probe:
         out["box_probe"] = probe
     print(json.dumps(out))
