@@ -140,12 +140,16 @@ int klf_run(klf_engine* e, const klf_filter* f, klf_result** out);
 
 /* ---- device-resident path (bench / callers that already hold bytes in HBM) ------- */
 /* Device layout helper: segment base offsets (256-B aligned, in stream order) and the
- * total device bytes to allocate (includes tail slack the kernels may over-read). */
+ * total device bytes to allocate (includes tail slack the kernels may over-read).  The pad
+ * between a stream's end and the next base and the slack may hold any bytes (klf_run leaves
+ * an earlier batch's there), and a stream whose length is a multiple of 256 is followed at
+ * once by the next one.  Results do not depend on any byte outside [seg_base, seg_base + len). */
 int klf_layout(uint32_t n_streams, const uint64_t* lens, uint64_t* seg_base,
                uint64_t* total_alloc);
 /* Runs over streams already laid out in device memory at d_bytes + seg_base[i]
  * (d_bytes must be a 16-B aligned device allocation of >= total_alloc bytes from klf_layout;
- * KLF_EINVAL otherwise). */
+ * KLF_EINVAL otherwise).  The bytes between and behind the streams are the caller's: they
+ * are read, never written, and whatever they hold changes no result. */
 int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n_streams,
                    const uint64_t* seg_base, const uint64_t* lens, const klf_filter* f,
                    klf_result** out);
