@@ -259,6 +259,40 @@ int klf_result_group_bits(klf_result* r, uint32_t stream_id, const uint8_t** bit
  * tables are compiled on the first run that asks for counts).  Extends the size report of printLogSize
  * (cmd/root.go:279-309) with the new --grep / --match flags (:485-497). */
 int klf_result_pattern_counts(klf_result* r, uint32_t stream_id, uint64_t* counts, uint32_t cap, uint32_t* n);
+/* Histogram over time of the set the result was selected from (SPEC.md S4c; --histogram): per
+ * stream, the parsed lines of H = what klf_result_group_bits returns (M on a run's result or a
+ * klf_retail of one, G' after klf_regroup, G'' after klf_window; on an engine without patterns
+ * a run's result counts every parsed line) are counted by their instant ts: below `origin`
+ * (outside[2 i]), in bucket floor((ts - origin) / width_ns) when that is below n_buckets
+ * (counts[i * n_buckets + k]: bucket k is [origin + k w, origin + (k + 1) w), closed below and
+ * open above like the window), else at or above the end (outside[2 i + 1]).  ts - origin is
+ * taken in nanoseconds as an exact integer.  Per stream below + the buckets + above = |H| =
+ * klf_counts.matched (klf_counts.parsed on a run's result of an engine without patterns): like
+ * matched the histogram is taken before --since and --tail.  Timestamps need not ascend; every
+ * origin with nsec in [0, 1e9) is legal, also sec = INT64_MIN / INT64_MAX.
+ * Read-only: r stays the engine's latest result and stays valid, its output, bitmaps and counts
+ * are untouched, it can be windowed, regrouped or re-tailed afterwards, and the call may be
+ * repeated with other options.  Read again: the bitmap (L/8 bytes; the line meta, 2 L, without
+ * patterns) and, per line of H, its line-index entry (built now if the run left it out) and the
+ * first 32 bytes of the line in the batch, which must still be resident (klf_run_device: the
+ * caller's buffer).  counts: n_streams x n_buckets u64, row-major; outside (nullable): n_streams
+ * x 2 {below, above}; *ms (nullable): device time of the call's table memset and kernel.  A
+ * stream without bytes gets zeros.
+ * KLF_EINVAL (checked first, without touching the device): null r, o or counts; width_ns == 0;
+ * n_buckets == 0 or above KLF_HIST_MAX_BUCKETS; n_buckets * width_ns >= 2^63 (spans up to about
+ * 292 years); nsec outside [0, 1e9); non-zero flags or origin._reserved.  KLF_ESTATE: r is not
+ * the engine's latest result.  KLF_ETOOBIG: non-empty streams * (n_buckets + 2) > 2^24 (the
+ * device table stays within 128 MiB).  Replaces nothing in the reference; it extends the size
+ * report of printLogSize (cmd/root.go:279-309), like klf_result_pattern_counts.  Not promised:
+ * follow sessions and shard.run_split (their per-stream rows simply add). */
+#define KLF_HIST_MAX_BUCKETS 65536u
+typedef struct klf_hist_opts {
+  klf_time origin;     /* lower edge of bucket 0, inclusive */
+  uint64_t width_ns;   /* >= 1 */
+  uint32_t n_buckets;  /* 1 .. KLF_HIST_MAX_BUCKETS; n_buckets * width_ns < 2^63 */
+  uint32_t flags;      /* 0 */
+} klf_hist_opts;       /* 32 bytes */
+int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint64_t* counts, uint64_t* outside, double* ms);
 /* Position of the stream's last unparseable newline-terminated line, counted from the end
  * over the newline-terminated lines (1 = the last one; 0 = every terminated line parses).
  * The byte-range shards of one stream need it: kubelet emits the trailing

@@ -245,6 +245,10 @@ struct klf_engine {
   // klf_regroup: the selection bitmap G' (the layout of d_bits) and the regroup kernels'
   // chunk summaries; allocated by the first regroup, so a plain run pays nothing for them
   DevBuf d_gbits, d_gsum;
+  // klf_result_histogram: the per-segment table and its pinned readback, the engine's own (no
+  // result's buffer is touched); allocated by the first histogram
+  DevBuf d_thist;
+  HostBuf h_thist;
   // the latest run's global line index is still to be built (lazy index, dense path): the
   // k_scatter launch that builds it
   std::vector<klf::RunArgs> index_pending;
@@ -731,6 +735,8 @@ extern "C" void klf_close(klf_engine* e) {
   e->h_rb.release();
   e->h_acblk.release();
   e->h_hist.release();
+  e->d_thist.release();
+  e->h_thist.release();
   e->h_stage.release();
   for (DevBuf* b : {&e->d_ac_out, &e->d_ac_dict, &e->d_pcount, &e->d_pairs}) b->release();
   e->d_block.release();
@@ -2272,6 +2278,76 @@ extern "C" int klf_result_pattern_counts(klf_result* r, uint32_t id, uint64_t* c
       else if (m >= 0 && general) v = r->pcount[(size_t)s * cs.n_cids + (size_t)m];
     }
     counts[u] = v;
+  }
+  return KLF_OK;
+}
+
+extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint64_t* counts, uint64_t* outside,
+                                    double* ms) {
+  if (!r || !o || !counts) return KLF_EINVAL;
+  klf_engine* e = r->e;
+  if (o->width_ns == 0 || o->n_buckets == 0 || o->n_buckets > KLF_HIST_MAX_BUCKETS)
+    return set_err(e, KLF_EINVAL, "klf_result_histogram: width_ns and n_buckets must be at least 1, n_buckets at most 65536");
+  if (o->width_ns > (uint64_t)INT64_MAX / o->n_buckets)
+    return set_err(e, KLF_EINVAL, "klf_result_histogram: n_buckets * width_ns must stay below 2^63");
+  if (o->origin.nsec < 0 || o->origin.nsec >= 1000000000)
+    return set_err(e, KLF_EINVAL, "klf_result_histogram: nsec outside [0, 1e9)");
+  if (o->flags || o->origin._reserved)
+    return set_err(e, KLF_EINVAL, "klf_result_histogram: unknown flag bits or a non-zero _reserved");
+  if (r->gen != e->gen || e->last_gen != r->gen)
+    return set_err(e, KLF_ESTATE, "klf_result_histogram: not the latest run");
+  const uint32_t nsegs = (uint32_t)r->so.size(), nb = o->n_buckets;
+  const uint64_t row = (uint64_t)nb + 2;
+  if ((uint64_t)nsegs * row > (1ull << 24))
+    return set_err(e, KLF_ETOOBIG, "klf_result_histogram: non-empty streams * (n_buckets + 2) exceeds 2^24");
+  if (ms) *ms = 0.0;
+  memset(counts, 0, (size_t)r->n_streams * nb * 8);
+  if (outside) memset(outside, 0, (size_t)r->n_streams * 2 * 8);
+  if (!nsegs) return KLF_OK;
+  if (int rc = ensure_index(e)) return rc;
+  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+  const klf::RunArgs& a = e->last_args;
+  const uint64_t span = o->width_ns * nb;  // ns, < 2^63
+  klf::HistArgs g{};
+  // the bitmap r was selected from (klf_result_group_bits): G' / G'', M, or the parsed lines
+  g.bits_in = r->grouped ? e->d_gbits.as<uint32_t>() : r->has_bits ? e->d_bits.as<uint32_t>() : nullptr;
+  g.meta = a.meta;
+  g.line_off = a.line_off;
+  g.bytes = a.bytes;
+  g.segs = a.segs;
+  g.segout = a.segout;
+  g.nsegs = nsegs;
+  g.n_buckets = nb;
+  g.cap_lines = a.cap_lines;
+  g.nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
+  g.org_sec = o->origin.sec;
+  g.org_nsec = o->origin.nsec;
+  int64_t end_nsec = o->origin.nsec + (int64_t)(span % 1000000000ull), carry = 0;
+  if (end_nsec >= 1000000000) { end_nsec -= 1000000000; carry = 1; }
+  g.end_nsec = (int32_t)end_nsec;
+  g.end_open = __builtin_add_overflow(o->origin.sec, (int64_t)(span / 1000000000ull) + carry, &g.end_sec) ? 1u : 0u;
+  g.width_ns = o->width_ns;
+  g.width_s = o->width_ns % 1000000000ull == 0 && span / 1000000000ull < (1ull << 32)
+                  ? (uint32_t)(o->width_ns / 1000000000ull) : 0u;
+  const size_t tbytes = (size_t)nsegs * row * 8;
+  HIPCHK(e, e->d_thist.ensure(tbytes), "alloc histogram table");
+  HIPCHK(e, e->h_thist.ensure(tbytes), "alloc histogram readback");
+  g.table = e->d_thist.as<uint64_t>();
+  // (ev[0] / ev[5] bracket a run or a re-tail, whose result read them when it was made)
+  HIPCHK(e, klf::launch_hist(g, e->stream, e->ev[0], e->ev[5], e->num_cus), "launch k_hist");
+  HIPCHK(e, hipMemcpyAsync(e->h_thist.p, e->d_thist.p, tbytes, hipMemcpyDeviceToHost, e->stream), "D2H histogram");
+  HIPCHK(e, hipStreamSynchronize(e->stream), "sync histogram");
+  if (ms) {
+    float f = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&f, e->ev[0], e->ev[5]), "histogram timing");
+    *ms = f;
+  }
+  const uint64_t* tab = e->h_thist.as<uint64_t>();
+  for (uint32_t id = 0; id < r->n_streams; ++id) {
+    const int64_t s = r->seg_of[id];
+    if (s < 0) continue;
+    memcpy(counts + (size_t)id * nb, tab + (size_t)s * row, (size_t)nb * 8);
+    if (outside) memcpy(outside + (size_t)id * 2, tab + (size_t)s * row + nb, 16);
   }
   return KLF_OK;
 }

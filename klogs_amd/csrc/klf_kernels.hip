@@ -3007,8 +3007,10 @@ __device__ __forceinline__ bool dig_ge(const uint32_t (&p)[6], const uint32_t (&
   const uint64_t c0 = (uint64_t)c[0] << 32 | c[1], c1 = (uint64_t)c[2] << 32 | c[3], c2 = (uint64_t)c[4] << 32 | c[5];
   return a0 > c0 || (a0 == c0 && (a1 > c1 || (a1 == c1 && a2 >= c2)));
 }
-__device__ __forceinline__ bool tw_line_in(const WindowArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
-                                           uint64_t seg_len) {
+// The first 32 bytes of the line at segp + off, packed: true iff they are the canonical
+// kubelet prefix with a year in 1970..2099, p = its 23 digits big-endian (Y Y Y Y | M M D D |
+// h h m m | s s n0 n1 | n2 n3 n4 n5 | n6 n7 '0' n8).
+__device__ __forceinline__ bool tw_canon_digits(const uint8_t* __restrict__ segp, uint64_t off, uint32_t (&p)[6]) {
   // two unaligned 16-B global loads at the line start (inside the allocation: kAllocSlack)
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   u32x4 x0, x1;
@@ -3019,18 +3021,22 @@ __device__ __forceinline__ bool tw_line_in(const WindowArgs& g, const uint8_t* _
   const uint32_t sep = ((w[1] ^ 0x2D00002Du) & 0xFF0000FFu) | ((w[2] ^ 0x00540000u) & 0x00FF0000u) |
                        ((w[3] ^ 0x00003A00u) & 0x0000FF00u) | ((w[4] ^ 0x2E00003Au) & 0xFF0000FFu) |
                        ((w[7] ^ 0x00205A00u) & 0x00FFFF00u);
-  const uint32_t p[6] = {__builtin_amdgcn_perm(0u, w[0], 0x00010203u),                   // Y Y Y Y
-                         __builtin_amdgcn_perm(w[2], w[1], 0x01020405u),                 // M M D D
-                         __builtin_amdgcn_perm(w[3], w[2], 0x03040607u),                 // h h m m
-                         __builtin_amdgcn_perm(w[5], w[4], 0x01020405u),                 // s s n0 n1
-                         __builtin_amdgcn_perm(w[6], w[5], 0x02030405u),                 // n2 n3 n4 n5
-                         __builtin_amdgcn_perm(w[7], w[6], 0x02030C04u) | 0x00003000u};  // n6 n7 0 n8
+  p[0] = __builtin_amdgcn_perm(0u, w[0], 0x00010203u);                   // Y Y Y Y
+  p[1] = __builtin_amdgcn_perm(w[2], w[1], 0x01020405u);                 // M M D D
+  p[2] = __builtin_amdgcn_perm(w[3], w[2], 0x03040607u);                 // h h m m
+  p[3] = __builtin_amdgcn_perm(w[5], w[4], 0x01020405u);                 // s s n0 n1
+  p[4] = __builtin_amdgcn_perm(w[6], w[5], 0x02030405u);                 // n2 n3 n4 n5
+  p[5] = __builtin_amdgcn_perm(w[7], w[6], 0x02030C04u) | 0x00003000u;   // n6 n7 0 n8
   const uint32_t hi = ((p[0] ^ 0x30303030u) | (p[1] ^ 0x30303030u) | (p[2] ^ 0x30303030u) | (p[3] ^ 0x30303030u) |
                        (p[4] ^ 0x30303030u) | (p[5] ^ 0x30303030u)) & 0xF0F0F0F0u;
   const uint32_t lo = ((p[0] + 0x06060606u) | (p[1] + 0x06060606u) | (p[2] + 0x06060606u) | (p[3] + 0x06060606u) |
                        (p[4] + 0x06060606u) | (p[5] + 0x06060606u)) & 0x40404040u;
-  if ((sep | hi | lo) == 0u && p[0] - 0x31393730u <= 0x32303939u - 0x31393730u)  // canonical, year 1970..2099
-    return dig_ge(p, g.from_dig) && !dig_ge(p, g.until_dig);
+  return (sep | hi | lo) == 0u && p[0] - 0x31393730u <= 0x32303939u - 0x31393730u;  // canonical, year 1970..2099
+}
+__device__ __forceinline__ bool tw_line_in(const WindowArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
+                                           uint64_t seg_len) {
+  uint32_t p[6];
+  if (tw_canon_digits(segp, off, p)) return dig_ge(p, g.from_dig) && !dig_ge(p, g.until_dig);
   TsResult r;
   uint32_t plen;
   if (!parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) return false;
@@ -3089,6 +3095,98 @@ __global__ __launch_bounds__(256) void k_tw_build(WindowArgs g) {
     }
     __syncthreads();
     if (w < nw) g.bits_out[w] = s_out[wv][lane];
+  }
+}
+
+// ====================================== histogram over time (klf_result_histogram, SPEC.md S4c) ==
+// Per stream, the lines of a selection bitmap H counted by instant: below `origin`, in one of
+// n_buckets buckets of width_ns from `origin` on, or at / above `end` = origin + n_buckets *
+// width_ns.  The walk is k_tw_build's (lane i of round r takes the wave's (64 r + i)-th line of
+// H and reads the first 32 bytes of that line); in place of a bit per line each line gets a key
+// = segment * (n_buckets + 2) + slot (slot n_buckets = below, n_buckets + 1 = above) into the
+// u64 table.  The 64 consecutive lines of a round mostly share a key, so a lane adds only when
+// its key differs from the previous lane's, and adds the length of its run of equal keys (from
+// the ballot of those heads): any order of keys stays exact, at one atomic per line at worst.
+
+// The instant of a canonical prefix from its packed digits (tw_canon_digits; a parsed line,
+// so every field is in range): days-from-civil plus h / m / s.
+__device__ __forceinline__ uint32_t dig2(uint32_t x) { return (x >> 8 & 15u) * 10u + (x & 15u); }
+__device__ __forceinline__ void canon_instant(const uint32_t (&p)[6], int64_t& sec, int32_t& nsec) {
+  const int32_t year = (int32_t)(dig2(p[0] >> 16) * 100u + dig2(p[0]));
+  const int32_t days = (int32_t)days_from_civil(year, (int)dig2(p[1] >> 16), (int)dig2(p[1]));  // 0 .. 47481
+  sec = (int64_t)days * 86400 + (int64_t)(dig2(p[2] >> 16) * 3600u + dig2(p[2]) * 60u + dig2(p[3] >> 16));
+  nsec = (int32_t)(dig2(p[3]) * 10000000u + (dig2(p[4] >> 16) * 100u + dig2(p[4])) * 1000u + dig2(p[5] >> 16) * 10u +
+                   (p[5] & 15u));
+}
+
+// The table slot of the line at segp + off, or ~0u for a line without an instant (none in H).
+__device__ __forceinline__ uint32_t hist_slot(const HistArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
+                                              uint64_t seg_len) {
+  uint32_t p[6];
+  int64_t sec;
+  int32_t nsec;
+  if (tw_canon_digits(segp, off, p)) {
+    canon_instant(p, sec, nsec);
+  } else {
+    TsResult r;
+    uint32_t plen;
+    if (!parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) return ~0u;
+    sec = r.sec;
+    nsec = r.nsec;
+  }
+  if (time_before(sec, nsec, g.org_sec, g.org_nsec)) return g.n_buckets;
+  if (!g.end_open && !time_before(sec, nsec, g.end_sec, g.end_nsec)) return g.n_buckets + 1;
+  // origin <= ts < end: d = ts - origin in ns lies in [0, n_buckets * width_ns), below 2^63
+  const uint64_t ds = (uint64_t)sec - (uint64_t)g.org_sec;
+  if (g.width_s)  // whole seconds and a span below 2^32 s: floor(d / 1e9) = ds - borrow, a 32-bit division
+    return ((uint32_t)ds - (nsec < g.org_nsec ? 1u : 0u)) / g.width_s;
+  const uint64_t d = ds * 1000000000ull + (uint64_t)(int64_t)(nsec - g.org_nsec);
+  return (uint32_t)(d / g.width_ns);
+}
+
+__global__ __launch_bounds__(256) void k_hist(HistArgs g) {
+  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
+  const uint32_t row = g.n_buckets + 2;
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    uint32_t in = 0;
+    if (l0 < L) in = g.bits_in ? g.bits_in[w] & word_range_mask(w, 0, L) : parsed_word(g.meta, w, L);
+    const uint32_t cnt = (uint32_t)__popc(in);
+    const uint32_t incl = wave_incl_scan_add(cnt, lane);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of H
+    __syncthreads();  // (the previous chunk's words are read)
+    s_in[wv][lane] = in;
+    s_pre[wv][lane] = incl - cnt;
+    s_seg[wv][lane] = in ? find_seg_by_line(g.segout, g.nsegs, l0) : 0u;
+    __syncthreads();
+    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
+    for (uint32_t k0 = 0; k0 < total; k0 += 64) {   // (total is wave-uniform: every lane takes every round)
+      const uint32_t k = k0 + (uint32_t)lane;
+      uint32_t key = ~0u;  // no line, or a line without an instant
+      if (k < total) {
+        uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
+#pragma unroll
+        for (uint32_t step = 32; step >= 1; step >>= 1)
+          if (s_pre[wv][j + step] <= k) j += step;
+        const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
+        const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
+        uint32_t s = s_seg[wv][j];
+        while (l >= g.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
+        const SegDesc sd = g.segs[s];
+        const uint32_t slot = hist_slot(g, g.bytes + sd.base, g.line_off[l + s], sd.len);
+        if (slot < row) key = s * row + slot;  // (< nsegs * row <= 2^24: the host's size check)
+      }
+      const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
+      const bool head = lane == 0 || key != prev;
+      const uint64_t heads = __ballot(head);
+      if (head && key != ~0u) {
+        const uint64_t after = lane == 63 ? 0ull : heads >> (lane + 1);  // the heads behind this lane
+        const uint32_t run = after ? (uint32_t)__ffsll((long long)after) : 64u - (uint32_t)lane;
+        atomicAdd(reinterpret_cast<unsigned long long*>(g.table + key), (unsigned long long)run);
+      }
+    }
   }
 }
 
@@ -4930,6 +5028,18 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
   if ((e = launch_tail_stage(a, st, ev, num_cus, m)) != hipSuccess) return e;
   if ((e = hipEventRecord(ev[5], st)) == hipSuccess) m |= 1u << 5;
   return e;
+}
+
+hipError_t launch_hist(const HistArgs& g, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int num_cus) {
+  hipError_t e = hipEventRecord(ev0, st);
+  if (e != hipSuccess) return e;
+  if ((e = hipMemsetAsync(g.table, 0, (size_t)g.nsegs * (g.n_buckets + 2) * 8, st)) != hipSuccess) return e;
+  if (g.nchunks) {
+    const uint64_t gmax = (uint64_t)num_cus * 16;
+    hipLaunchKernelGGL(k_hist, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipEventRecord(ev1, st);
 }
 
 }  // namespace klf

@@ -401,6 +401,29 @@ struct WindowArgs {
   uint32_t from_dig[6], until_dig[6];  // the bounds packed like RunArgs::since_dig
 };
 
+// Histogram over time of a finished run's selection (klf_result_histogram, SPEC.md S4c): k_hist
+// walks a selection bitmap as k_tw_build does and counts each of its lines, by stream, below
+// `org`, in bucket floor((ts - org) / width_ns), or at / above `end` = org + n_buckets * width_ns.
+// It writes the table alone: the run's arrays are only read.
+struct HistArgs {
+  const uint32_t* bits_in;  // M, G' or G'', [cap_lines / 32 + 1]; null: the parsed lines (no patterns)
+  const uint16_t* meta;     // [cap_lines]
+  const uint64_t* line_off; // [cap_lines + nsegs] the run's line index
+  const uint8_t* bytes;     // the batch
+  const SegDesc* segs;      // [nsegs]
+  const SegOut* segout;     // [nsegs]
+  uint32_t nsegs;
+  uint32_t n_buckets;
+  uint64_t cap_lines;
+  uint64_t nchunks;         // kMatchChunk chunks holding lines
+  int64_t org_sec, end_sec;
+  int32_t org_nsec, end_nsec;
+  uint32_t end_open;        // org + the span leaves int64 seconds: no line is above
+  uint32_t width_s;         // width_ns / 1e9 when that is exact and the span is below 2^32 s, else 0
+  uint64_t width_ns;
+  uint64_t* table;          // [nsegs * (n_buckets + 2)] per segment: the buckets, below, above (zeroed by launch_hist)
+};
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]
@@ -422,6 +445,8 @@ hipError_t launch_pipeline(const RunArgs& a, hipStream_t stream, hipEvent_t* ev,
 hipError_t launch_retail(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus,
                          uint32_t* ev_mask = nullptr, const RegroupArgs* g = nullptr,
                          const WindowArgs* tw = nullptr);
+// Zeroes g.table and counts into it (k_hist), between the events ev0 and ev1.
+hipError_t launch_hist(const HistArgs& g, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int num_cus);
 // Data statistics (kGramHistWords u32, zeroed here) of the first `sample` bytes of each of
 // up to 16 segments: byte counts, and the 2-grams at even offsets (folded like the
 // prefilter's grams).

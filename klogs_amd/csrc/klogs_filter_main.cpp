@@ -2,7 +2,7 @@
 // over captured log bodies, with the filter on the GPU through libklf.
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
-//                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X]
+//                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
 //
 // -A / -B / -C N (lines of context after / before / around a matching line) and
@@ -13,6 +13,11 @@
 // klf_window), before --since and --tail apply: X is an RFC3339Nano instant or a Go duration
 // meaning that long before --now.  They work with and without a pattern and combine with the
 // context flags in one call.
+//
+// --histogram WIDTH (a Go duration > 0) also writes <logpath>/histogram.tsv: per stream, the
+// lines of the selection (after the pattern, the context flags and the window; before --since
+// and --tail, SPEC.md S4c, klf_result_histogram) counted in buckets of WIDTH from --from (else
+// the --since instant; one of the two is needed) up to --until (else --now), at most 65536.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -66,6 +71,10 @@ void usage() {
                "                    context after / before / around a match; the lines that do not match)\n"
                "                    [--from X] [--until X]   (the lines with from <= timestamp < until, before\n"
                "                    --since / --tail apply; X: an RFC3339Nano instant, or a duration before --now)\n"
+               "                    [--histogram WIDTH]   (also writes <logpath>/histogram.tsv: the selected lines\n"
+               "                    per stream in buckets of WIDTH, a duration > 0, from --from (else the --since\n"
+               "                    instant; one of them is needed) up to --until (else --now), at most 65536\n"
+               "                    buckets; counted before --since / --tail apply)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -83,6 +92,8 @@ int main(int argc, char** argv) {
   bool regrouped = false;  // any of -A / -B / -C / --invert-match
   std::string from_arg, until_arg;
   bool from_set = false, until_set = false;  // --from / --until
+  std::string hist_arg;
+  bool hist_set = false;  // --histogram
   auto context = [&](const std::string& v) -> uint32_t {
     char* end = nullptr;
     const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
@@ -108,6 +119,7 @@ int main(int argc, char** argv) {
     else if (a == "--invert-match") { regroup.flags |= KLF_REGROUP_INVERT; regrouped = true; }
     else if (a == "--from") { from_arg = val(); from_set = true; }
     else if (a == "--until") { until_arg = val(); until_set = true; }
+    else if (a == "--histogram") { hist_arg = val(); hist_set = true; }
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -152,6 +164,21 @@ int main(int argc, char** argv) {
   char err[512] = {0};
   if (klh_lop_opts(since.c_str(), tail, now, &filter, &rejected, err, sizeof(err)) != KLH_OK) panic_exit(err);
   filter.flags |= KLF_FILTER_NO_TIMING;  // (the CLI reads no device timing)
+
+  // --histogram: buckets of WIDTH over [--from, else the --since instant; --until, else now)
+  klf_hist_opts hist{{0, 0, 0}, 0, 0, 0};
+  if (hist_set) {
+    int64_t w = 0;
+    char perr[256];
+    if (klh_parse_duration(hist_arg.c_str(), &w, perr, sizeof(perr)) != KLH_OK || w <= 0) usage();
+    if (!from_set && since.empty()) usage();  // no lower edge
+    const klf_time lo = from_set ? window.from : filter.since, hi = until_set ? window.until : now;
+    const __int128 span = ((__int128)hi.sec - lo.sec) * 1000000000 + (hi.nsec - lo.nsec);
+    if (span <= 0) usage();
+    const __int128 nb = (span + w - 1) / w;
+    if (nb > KLF_HIST_MAX_BUCKETS || nb * w > (__int128)INT64_MAX) usage();
+    hist = klf_hist_opts{{lo.sec, lo.nsec, 0}, (uint64_t)w, (uint32_t)nb, 0};
+  }
 
   // the pod selection, grouped by pod in first-appearance order
   std::vector<PodEnt> pods;
@@ -260,6 +287,36 @@ int main(int argc, char** argv) {
       if (rc != KLF_OK) panic_exit(std::string("klf_regroup: ") + klf_strerror(rc) + ": " + klf_last_error(e));
       klf_result_free(r);
       r = g;
+    }
+    if (hist_set) {  // over the result that gets written, before it is
+      std::vector<uint64_t> hc((size_t)n * hist.n_buckets), ho((size_t)n * 2);
+      rc = klf_result_histogram(r, &hist, hc.data(), ho.data(), nullptr);
+      if (rc != KLF_OK) panic_exit(std::string("klf_result_histogram: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      const std::string hpath = logpath + "/histogram.tsv";
+      FILE* hf = std::fopen(hpath.c_str(), "w");
+      if (!hf) panic_exit("create " + hpath);
+      std::fprintf(hf, "Pod\tContainer\tBucket\tLines\n");
+      for (uint32_t i = 0; i < n; ++i) {
+        const char* pod = pods[table[i].pod].name.c_str();
+        if (ho[2 * (size_t)i])
+          std::fprintf(hf, "%s\t%s\tbelow\t%llu\n", pod, cname[i].c_str(), (unsigned long long)ho[2 * (size_t)i]);
+        for (uint32_t k = 0; k < hist.n_buckets; ++k) {
+          const uint64_t c = hc[(size_t)i * hist.n_buckets + k];
+          if (!c) continue;
+          const __int128 t = (__int128)hist.origin.sec * 1000000000 + hist.origin.nsec + (__int128)k * hist.width_ns;
+          __int128 sec = t / 1000000000, ns = t % 1000000000;
+          if (ns < 0) { ns += 1000000000; --sec; }
+          const time_t ts = (time_t)sec;
+          struct tm tm;
+          gmtime_r(&ts, &tm);
+          std::fprintf(hf, "%s\t%s\t%04d-%02d-%02dT%02d:%02d:%02d.%09dZ\t%llu\n", pod, cname[i].c_str(),
+                       tm.tm_year + 1900, tm.tm_mon + 1, tm.tm_mday, tm.tm_hour, tm.tm_min, tm.tm_sec, (int)ns,
+                       (unsigned long long)c);
+        }
+        if (ho[2 * (size_t)i + 1])
+          std::fprintf(hf, "%s\t%s\tabove\t%llu\n", pod, cname[i].c_str(), (unsigned long long)ho[2 * (size_t)i + 1]);
+      }
+      if (std::fclose(hf) != 0) panic_exit("close " + hpath);
     }
     // writeLogToDisk (:359-374): one klf_result_write over every stream's file (chunked,
     // double-buffered D2H from pinned memory), files closed afterwards

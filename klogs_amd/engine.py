@@ -30,6 +30,7 @@ KLF_PAT_REGEX = 1
 GO_ZERO_TIME = (-62135596800, 0)
 TIME_MIN_SEC = -(1 << 63)     # KLF_TIME_MIN_SEC: klf_window_opts.from.sec, open below
 TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, open above
+HIST_MAX_BUCKETS = 65536      # KLF_HIST_MAX_BUCKETS: klf_hist_opts.n_buckets at most
 
 MODE_NAMES = {0: "none", 1: "never", 2: "all", 3: "literal1", 4: "general"}
 
@@ -66,6 +67,10 @@ class _WindowOpts(C.Structure):
                 ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class _HistOpts(C.Structure):
+    _fields_ = [("origin", _Time), ("width_ns", C.c_uint64), ("n_buckets", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class _Counts(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("parsed", C.c_uint64), ("since_ok", C.c_uint64),
                 ("matched", C.c_uint64), ("selected", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -98,6 +103,8 @@ SIGNATURES = {
     "klf_result_group_bits": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "klf_result_pattern_counts": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32,
                                             C.POINTER(C.c_uint32)]),
+    "klf_result_histogram": (C.c_int, [C.c_void_p, C.POINTER(_HistOpts), C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_double)]),
     "klf_result_last_unparsed": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "klf_result_device_out": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint64)]),
@@ -302,6 +309,7 @@ class Result:
         self._p = C.c_void_p(ptr)
         self.n_streams = n_streams
         self._eng = eng
+        self.hist_ms = 0.0  # device time of the last histogram() call
 
     def stream(self, i: int) -> StreamOut:
         p = C.c_void_p()
@@ -343,6 +351,30 @@ class Result:
         buf = (C.c_uint64 * max(1, n.value))()
         _check(_lib.klf_result_pattern_counts(self._p, i, buf, n.value, C.byref(n)), self._eng._h)
         return [int(x) for x in buf[: n.value]]
+
+    def histogram(self, origin: Tuple[int, int], width_ns: int, n_buckets: int) -> Tuple[np.ndarray, np.ndarray]:
+        """klf_result_histogram (SPEC.md S4c): the lines of the set this result was selected from
+        (M, G' or G''; the parsed lines without patterns), before --since and --tail, counted per
+        stream by instant.  Returns (counts, outside): counts[i, k] = stream i's lines in
+        [origin + k width_ns, origin + (k + 1) width_ns), outside[i] = (below origin, at or above
+        the end), both np.uint64.  Read-only: this result stays the latest and valid.  The device
+        time of the call (ms) is left in `self.hist_ms`.  Needs the stream count the result was
+        made with (run(..., n_streams=)): ValueError when it is not the result's."""
+        n = self.n_streams  # the library fills one row per stream of the result: the arrays must match
+        if (_lib.klf_result_stream(self._p, n, None, None, None) != KLF_EINVAL
+                or (n and _lib.klf_result_stream(self._p, n - 1, None, None, None) == KLF_EINVAL)):
+            raise ValueError(f"histogram: the result does not have n_streams = {n} streams")
+        o = _HistOpts()
+        o.origin.sec, o.origin.nsec = int(origin[0]), int(origin[1])
+        o.width_ns, o.n_buckets = int(width_ns), int(n_buckets)
+        rows = max(1, self.n_streams)
+        counts = np.zeros((rows, max(1, min(int(n_buckets), HIST_MAX_BUCKETS))), dtype=np.uint64)
+        outside = np.zeros((rows, 2), dtype=np.uint64)
+        ms = C.c_double()
+        _check(_lib.klf_result_histogram(self._p, C.byref(o), C.c_void_p(counts.ctypes.data),
+                                         C.c_void_p(outside.ctypes.data), C.byref(ms)), self._eng._h)
+        self.hist_ms = float(ms.value)
+        return counts[: self.n_streams], outside[: self.n_streams]
 
     def last_unparsed(self, i: int) -> int:
         """klf_result_last_unparsed: rank from the end (over newline-terminated lines) of the
