@@ -343,6 +343,60 @@ int klf_result_index_mode(const klf_result* r);
 int klf_result_compaction(const klf_result* r);
 void klf_result_free(klf_result* r);
 
+/* ---- merged timeline (SPEC.md S4d; --merge) ---------------------------------------- */
+/* The emitted lines of all streams of a finished run in one chronological sequence.  For a
+ * result r that is the engine's latest (a run's, or a klf_retail / klf_regroup / klf_window
+ * result; with or without patterns, any compaction), E(i) = the lines of stream i whose
+ * contents make up r's output for that stream (after since and the tail rule;
+ * |E(i)| = klf_counts.selected).  The timeline is the union of the E(i) ordered by
+ * (ts.sec, ts.nsec, stream id, line number): equal instants keep stream order, then input
+ * order; timestamps need not ascend within a stream; offsets compare by instant.  Entry k
+ * renders as tag[stream] + P + content + N: the caller's tag bytes of the stream (none with
+ * tags == NULL), P = the line's prefix up to and including its first space with
+ * KLF_TIMELINE_TIMESTAMPS (else nothing), the S1 content, and N = "\n" iff the line has no
+ * terminating '\n' (an emitted trailing fragment never glues onto the next entry).  The merged
+ * bytes are the rendered entries in timeline order.
+ * Read-only like klf_result_histogram: r stays the latest result and stays valid, its output,
+ * bitmaps and counts are untouched, and the call may be repeated with other options.  Read
+ * again: the selection bitmap, the line meta, per emitted line its line-index entry (built now
+ * if the run left it out) and its bytes in the batch, which must still be resident.
+ * A timeline owns its device and host buffers: it stays valid through later runs and
+ * klf_reset until klf_timeline_free, which must come before klf_close.  The sort's scratch
+ * is freed before klf_result_timeline returns.  Host views copy D2H on first access.
+ * klf_timeline_entries: entry k's rendered length is off[k + 1] - off[k], the last one's
+ * len - off[n - 1].  klf_timeline_bytes with bytes == NULL gives the length only (no copy).
+ * klf_timeline_write appends the merged bytes to fd through the pinned double-buffered D2H
+ * path of klf_result_write (EINTR and short writes retried, KLF_EIO).  klf_timeline_ms: device
+ * time of the call, first launch to last.
+ * KLF_EINVAL (checked first, without touching the device): null r, o or out; unknown flag
+ * bits; non-zero _reserved; tags with a null tag_off; tag_off not ascending; a tag longer than
+ * KLF_TIMELINE_MAX_TAG.  KLF_ESTATE: r is not the engine's latest result.  KLF_ETOOBIG: more
+ * than 2^32 - 1 entries.  KLF_ENOMEM: an allocation failed.  A result with no emitted line
+ * gives a valid empty timeline (n = 0, len = 0).  Not promised: follow sessions (a flush's
+ * timeline covers that flush) and shard.run_split.  Replaces nothing in the reference, whose
+ * per-container files (cmd/root.go:341-374) stay as they are. */
+#define KLF_TIMELINE_TIMESTAMPS 1u
+#define KLF_TIMELINE_MAX_TAG 1024u
+typedef struct klf_timeline klf_timeline;
+typedef struct klf_timeline_opts {
+  const uint8_t* tags;      /* all tags concatenated; NULL = no tags (tag_off ignored) */
+  const uint32_t* tag_off;  /* n_streams + 1 offsets into tags */
+  uint32_t flags, _reserved;
+} klf_timeline_opts;
+typedef struct klf_timeline_entry {  /* 32 bytes */
+  int64_t sec;
+  int32_t nsec;
+  uint32_t stream;
+  uint64_t line;  /* 0-based in its stream */
+  uint64_t off;   /* start in the merged bytes */
+} klf_timeline_entry;
+int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, klf_timeline** out);
+int klf_timeline_entries(klf_timeline* t, const klf_timeline_entry** e, uint64_t* n);
+int klf_timeline_bytes(klf_timeline* t, const uint8_t** bytes, uint64_t* len);
+int klf_timeline_write(klf_timeline* t, int fd, uint64_t* written);
+int klf_timeline_ms(const klf_timeline* t, double* ms);
+void klf_timeline_free(klf_timeline* t);
+
 /* ---- follow mode (-f) -------------------------------------------- */
 /* The reference streams each container until EOF with Follow set (cmd/root.go:217-218,
  * streamLog :312-339, the "ended prematurely" warning :314-318) while the main goroutine

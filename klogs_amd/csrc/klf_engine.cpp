@@ -2352,6 +2352,250 @@ extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint6
   return KLF_OK;
 }
 
+// ------------------------------------------------------------- merged timeline ---
+
+// A timeline owns what it returns: the entry records and the merged bytes on the device, and
+// their host copies once a view asked for them.  Nothing of the engine's workspace is kept.
+struct klf_timeline {
+  klf_engine* e = nullptr;
+  uint64_t n = 0, len = 0;
+  double ms = 0.0;
+  DevBuf d_entries, d_bytes;
+  bool have_entries = false, have_bytes = false;
+  std::vector<klf_timeline_entry> entries;
+  std::vector<uint8_t> bytes;
+  ~klf_timeline() {
+    d_entries.release();
+    d_bytes.release();
+  }
+};
+static_assert(sizeof(klf_timeline_entry) == sizeof(klf::TlEntry) && sizeof(klf_timeline_entry) == 32,
+              "klf_timeline_entry is the kernels' TlEntry");
+
+namespace {
+// The call's scratch: the chunk bases, both item buffers, the side records, the histograms, the
+// block counts and sums, the tag tables; freed when klf_result_timeline returns.
+struct TlScratch {
+  DevBuf cbase, items[2], side, dhist, bcnt, psum, segtab, tags;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~TlScratch() {
+    for (DevBuf* b : {&cbase, &items[0], &items[1], &side, &dhist, &bcnt, &psum, &segtab, &tags}) b->release();
+    for (auto& x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+}  // namespace
+
+static int tl_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
+  const hipError_t h = b.ensure(bytes);
+  if (h == hipSuccess) return KLF_OK;
+  (void)hipGetLastError();
+  if (h == hipErrorOutOfMemory)
+    return set_err(e, KLF_ENOMEM, std::string("klf_result_timeline: alloc ") + what);
+  return hip_err(e, h, what);
+}
+
+extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, klf_timeline** out) {
+  if (!r || !o || !out) return KLF_EINVAL;
+  klf_engine* e = r->e;
+  if ((o->flags & ~KLF_TIMELINE_TIMESTAMPS) || o->_reserved)
+    return set_err(e, KLF_EINVAL, "klf_result_timeline: unknown flag bits or a non-zero _reserved");
+  if (o->tags && !o->tag_off) return set_err(e, KLF_EINVAL, "klf_result_timeline: tags without tag_off");
+  if (o->tags)
+    for (uint32_t i = 0; i < r->n_streams; ++i) {
+      if (o->tag_off[i + 1] < o->tag_off[i]) return set_err(e, KLF_EINVAL, "klf_result_timeline: tag_off must ascend");
+      if (o->tag_off[i + 1] - o->tag_off[i] > KLF_TIMELINE_MAX_TAG)
+        return set_err(e, KLF_EINVAL, "klf_result_timeline: a tag is longer than KLF_TIMELINE_MAX_TAG");
+    }
+  if (r->gen != e->gen || e->last_gen != r->gen)
+    return set_err(e, KLF_ESTATE, "klf_result_timeline: not the latest run");
+  std::unique_ptr<klf_timeline> t(new (std::nothrow) klf_timeline());
+  if (!t) return KLF_ENOMEM;
+  t->e = e;
+  const uint32_t nsegs = (uint32_t)r->so.size();
+  if (!nsegs) {  // no stream has bytes
+    *out = t.release();
+    return KLF_OK;
+  }
+  if (int rc = ensure_index(e)) return rc;
+  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+  hipStream_t st = e->stream;
+  TlScratch sc;
+  klf::TlArgs g{};
+  g.a = e->last_args;
+  // the bitmap r was selected over (klf_result_group_bits): G' / G'', M, or every line
+  g.bits_in = r->grouped ? e->d_gbits.as<uint32_t>() : r->has_bits ? e->d_bits.as<uint32_t>() : nullptr;
+  g.nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
+  g.timestamps = (o->flags & KLF_TIMELINE_TIMESTAMPS) ? 1u : 0u;
+  // per segment: its stream id and its tag
+  std::vector<uint32_t> segtab((size_t)nsegs * 3, 0u);
+  for (uint32_t id = 0; id < r->n_streams; ++id) {
+    const int64_t s = r->seg_of[id];
+    if (s < 0) continue;
+    segtab[3 * (size_t)s] = id;
+    if (o->tags) {
+      segtab[3 * (size_t)s + 1] = o->tag_off[id];
+      segtab[3 * (size_t)s + 2] = o->tag_off[id + 1] - o->tag_off[id];
+    }
+  }
+  const uint32_t tag_bytes = o->tags ? o->tag_off[r->n_streams] : 0u;
+  if (int rc = tl_alloc(e, sc.segtab, segtab.size() * 4, "segment table")) return rc;
+  HIPCHK(e, hipMemcpyAsync(sc.segtab.p, segtab.data(), segtab.size() * 4, hipMemcpyHostToDevice, st), "H2D segment table");
+  g.segtab = sc.segtab.as<uint32_t>();
+  if (tag_bytes) {
+    if (int rc = tl_alloc(e, sc.tags, tag_bytes, "tags")) return rc;
+    HIPCHK(e, hipMemcpyAsync(sc.tags.p, o->tags, tag_bytes, hipMemcpyHostToDevice, st), "H2D tags");
+    g.tags = sc.tags.as<uint8_t>();
+  }
+  if (int rc = tl_alloc(e, sc.cbase, (g.nchunks + 1) * 8, "chunk bases")) return rc;
+  g.cbase = sc.cbase.as<uint64_t>();
+  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "timeline events");
+  auto finish = [&]() -> int {  // the device time, first launch to last
+    HIPCHK(e, hipEventRecord(sc.ev[1], st), "record timeline end");
+    HIPCHK(e, hipStreamSynchronize(st), "sync timeline");
+    float f = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "timeline timing");
+    t->ms = f;
+    return KLF_OK;
+  };
+  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record timeline start");
+  // 1. E lines per chunk -> n
+  HIPCHK(e, klf::launch_tl_count(g, st, e->num_cus), "launch k_tl_count");
+  uint64_t n = 0;
+  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H timeline size");
+  HIPCHK(e, hipStreamSynchronize(st), "sync timeline size");
+  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_timeline: more than 2^32 - 1 entries");
+  if (!n) {
+    if (int rc = finish()) return rc;
+    *out = t.release();
+    return KLF_OK;
+  }
+  g.n = n;
+  // 2. keys and the digit histograms
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = tl_alloc(e, sc.items[k], n * sizeof(klf::TlItem), "sort items")) return rc;
+    g.items[k] = sc.items[k].as<klf::TlItem>();
+  }
+  if (int rc = tl_alloc(e, sc.side, n * sizeof(klf::TlSide), "side records")) return rc;
+  g.side = sc.side.as<klf::TlSide>();
+  if (int rc = tl_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
+  g.dhist = sc.dhist.as<uint64_t>();
+  HIPCHK(e, klf::launch_tl_keys(g, st, e->num_cus), "launch k_tl_keys");
+  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
+  HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
+  HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
+  // 3. the passes whose digit differs somewhere (one bin holding all n: nothing to move)
+  const size_t nblocks = (size_t)((n + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
+  uint32_t cur = 0;
+  for (uint32_t p = 0; p < klf::kTlDigits; ++p) {
+    bool one_bin = false;
+    for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n;
+    if (one_bin) continue;
+    if (!g.bcnt) {
+      if (int rc = tl_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
+      g.bcnt = sc.bcnt.as<uint32_t>();
+    }
+    HIPCHK(e, klf::launch_tl_pass(g, p, cur, st), "launch radix pass");
+    cur ^= 1u;
+  }
+  // 4. rendered lengths -> offsets, entries, bytes
+  const size_t pblocks = (size_t)((n + klf::kTlPlanBlock - 1) / klf::kTlPlanBlock);
+  if (int rc = tl_alloc(e, sc.psum, (pblocks + 1) * 8, "block sums")) return rc;
+  g.psum = sc.psum.as<uint64_t>();
+  HIPCHK(e, klf::launch_tl_plan(g, cur, st), "launch k_tl_plan");
+  uint64_t total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, g.psum + pblocks, 8, hipMemcpyDeviceToHost, st), "D2H merged length");
+  HIPCHK(e, hipStreamSynchronize(st), "sync merged length");
+  if (int rc = tl_alloc(e, t->d_entries, n * sizeof(klf::TlEntry), "entries")) return rc;
+  if (int rc = tl_alloc(e, t->d_bytes, total + 16, "merged bytes")) return rc;
+  g.entries = t->d_entries.as<klf::TlEntry>();
+  g.out = t->d_bytes.as<uint8_t>();
+  HIPCHK(e, klf::launch_tl_copy(g, cur, st), "launch k_tl_copy");
+  if (int rc = finish()) return rc;
+  t->n = n;
+  t->len = total;
+  *out = t.release();
+  return KLF_OK;
+}
+
+extern "C" int klf_timeline_entries(klf_timeline* t, const klf_timeline_entry** ent, uint64_t* n) {
+  if (!t || !ent || !n) return KLF_EINVAL;
+  klf_engine* e = t->e;
+  if (!t->have_entries && t->n) {
+    try { t->entries.resize((size_t)t->n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
+    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+    HIPCHK(e, hipMemcpy(t->entries.data(), t->d_entries.p, (size_t)t->n * sizeof(klf_timeline_entry), hipMemcpyDeviceToHost),
+           "D2H timeline entries");
+  }
+  t->have_entries = true;
+  *ent = t->entries.data();
+  *n = t->n;
+  return KLF_OK;
+}
+
+extern "C" int klf_timeline_bytes(klf_timeline* t, const uint8_t** bytes, uint64_t* len) {
+  if (!t || !len) return KLF_EINVAL;
+  *len = t->len;
+  if (!bytes) return KLF_OK;
+  klf_engine* e = t->e;
+  if (!t->have_bytes && t->len) {
+    try { t->bytes.resize((size_t)t->len); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
+    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+    HIPCHK(e, hipMemcpy(t->bytes.data(), t->d_bytes.p, (size_t)t->len, hipMemcpyDeviceToHost), "D2H merged bytes");
+  }
+  t->have_bytes = true;
+  *bytes = t->bytes.data();
+  return KLF_OK;
+}
+
+// klf_result_write's path for one descriptor: a pinned chunk from the staging pool, D2H in two
+// halves of it with the next half in flight while the current one is written.
+extern "C" int klf_timeline_write(klf_timeline* t, int fd, uint64_t* written) {
+  if (written) *written = 0;
+  if (!t || fd < 0) return KLF_EINVAL;
+  klf_engine* e = t->e;
+  if (!t->len) return KLF_OK;
+  if (t->have_bytes) {  // already on the host
+    if (!write_all(fd, t->bytes.data(), t->len))
+      return set_err(e, KLF_EIO, std::string("write merged timeline: ") + strerror(errno));
+    if (written) *written = t->len;
+    return KLF_OK;
+  }
+  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+  klf_engine::StageChunk c;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool ok = take_chunk(e, &c) && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
+                  hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) == hipSuccess;
+  WErr werr;
+  uint64_t total = 0;
+  const WPiece q{0, t->len, fd, 0, {}};
+  if (ok) (void)copy_part(e, t->d_bytes.as<uint8_t>(), q, 0, t->len, c.p, kStageChunk / 2, st, ev, werr, total);
+  if (st) (void)hipStreamSynchronize(st);  // no DMA into a chunk handed back below
+  for (auto& x : ev)
+    if (x) (void)hipEventDestroy(x);
+  if (st) (void)hipStreamDestroy(st);
+  if (c.p) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    c.used = 0;
+    e->chunk_pool.push_back(c);
+  }
+  if (written) *written = total;
+  if (!ok) return set_err(e, KLF_ENOMEM, "klf_timeline_write: setup (pinned chunk / HIP stream)");
+  if (werr.id.load() >= 0)
+    return set_err(e, KLF_EIO, "write merged timeline: " + werr.what + (werr.err ? std::string(": ") + strerror(werr.err) : std::string()));
+  return KLF_OK;
+}
+
+extern "C" int klf_timeline_ms(const klf_timeline* t, double* ms) {
+  if (!t || !ms) return KLF_EINVAL;
+  *ms = t->ms;
+  return KLF_OK;
+}
+
+extern "C" void klf_timeline_free(klf_timeline* t) { delete t; }
+
 extern "C" int klf_result_last_unparsed(klf_result* r, uint32_t id, uint64_t* rank) {
   int rc = check_result(r, id);
   if (rc) return rc;

@@ -3190,6 +3190,362 @@ __global__ __launch_bounds__(256) void k_hist(HistArgs g) {
   }
 }
 
+// ====================================== merged timeline (klf_result_timeline, SPEC.md S4d) ==
+// The emitted lines E of every stream (the lines l of [win_lo, win_hi) with parsed, since_ok
+// and their bit in the selection bitmap: window_lines' rule), keyed by instant, sorted by a
+// stable LSD radix sort (so equal instants keep their (stream, line) order) and rendered into
+// one buffer.  Every step is reduce-then-scan over kernel boundaries; no block waits on another.
+
+// The parsed-and-since_ok bits of word w's 32 lines (parsed_word's loads).
+__device__ __forceinline__ uint32_t sel_word(const uint16_t* __restrict__ meta, uint64_t w, uint64_t L) {
+  const uint64_t l0 = w * 32;
+  uint32_t p = 0;
+  if (l0 + 32 <= L) {
+    const uint4* q = reinterpret_cast<const uint4*>(meta + l0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 v = q[k];
+      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t y = x[j] & (x[j] >> 1);  // bit 0 / bit 16: both flags of the low / high line
+        p |= ((y & 1u) | ((y >> 15) & 2u)) << (8 * k + 2 * j);
+      }
+    }
+  } else {
+    for (uint64_t l = l0; l < L; ++l) {
+      const uint32_t m = meta[l];
+      p |= (m & (m >> 1) & 1u) << (l - l0);
+    }
+  }
+  return p;
+}
+
+// Word w of E (0 past the line count): the selection word, the tail windows of the streams the
+// word meets, then the parsed / since_ok flags (read only where something is left).
+__device__ __forceinline__ uint32_t tl_e_word(const TlArgs& g, uint64_t w, uint64_t L) {
+  const uint64_t l0 = w * 32;
+  if (l0 >= L) return 0u;
+  uint32_t x = word_range_mask(w, 0, L);
+  if (g.bits_in) x &= g.bits_in[w];
+  if (!x) return 0u;
+  const uint64_t l1 = l0 + 32 < L ? l0 + 32 : L;
+  uint32_t win = 0;
+  for (uint32_t s = find_seg_by_line(g.a.segout, g.a.nsegs, l0); s < g.a.nsegs && g.a.segout[s].line_lo < l1; ++s)
+    win |= word_range_mask(w, g.a.segout[s].win_lo, g.a.segout[s].win_hi);
+  x &= win;
+  if (!x) return 0u;
+  return x & sel_word(g.a.meta, w, L);
+}
+
+__global__ __launch_bounds__(256) void k_tl_count(TlArgs g) {
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.a.segout[g.a.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t;
+    const uint32_t cnt = wave_sum((uint32_t)__popc(tl_e_word(g, w, L)));
+    __syncthreads();  // (the previous chunk's sums are read)
+    if (lane == 0) s_w[wv] = cnt;
+    __syncthreads();
+    if (t == 0) g.cbase[c] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  }
+}
+
+// One block: a[0 .. m) becomes its exclusive prefix, a[m] the total.
+__global__ __launch_bounds__(256) void k_tl_scan(uint64_t* __restrict__ a, uint64_t m) {
+  __shared__ uint64_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t per = (m + 255) / 256;
+  const uint64_t i0 = (uint64_t)t * per < m ? (uint64_t)t * per : m, i1 = i0 + per < m ? i0 + per : m;
+  uint64_t sum = 0;
+  for (uint64_t i = i0; i < i1; ++i) sum += a[i];
+  const uint64_t incl = wave_incl_scan_add(sum, lane);
+  if (lane == 63) s_w[wv] = incl;
+  __syncthreads();
+  uint64_t pre = incl - sum;
+  for (int k = 0; k < wv; ++k) pre += s_w[k];
+  for (uint64_t i = i0; i < i1; ++i) {
+    const uint64_t x = a[i];
+    a[i] = pre;
+    pre += x;
+  }
+  if (t == 255) a[m] = pre;  // (thread 255's range ends at m)
+}
+
+// The instant of the parsed line at segp + off (k_hist's two paths).
+__device__ __forceinline__ void tl_instant(const uint8_t* __restrict__ segp, uint64_t off, uint64_t seg_len,
+                                           int64_t& sec, int32_t& nsec) {
+  uint32_t p[6];
+  if (tw_canon_digits(segp, off, p)) {
+    canon_instant(p, sec, nsec);
+    return;
+  }
+  TsResult r;
+  uint32_t plen;
+  sec = 0;
+  nsec = 0;
+  if (parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) {
+    sec = r.sec;
+    nsec = r.nsec;
+  }
+}
+
+// k_hist's walk over E: lane i of round r takes the wave's (64 r + i)-th line of E.  Its rank
+// in (stream, line) order is the chunk's base + the lines of the block's earlier waves + k.
+__global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
+  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64], s_tot[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.a.segout[g.a.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t in = tl_e_word(g, w, L);
+    const uint32_t cnt = (uint32_t)__popc(in);
+    const uint32_t incl = wave_incl_scan_add(cnt, lane);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of E
+    __syncthreads();  // (the previous chunk's words are read)
+    s_in[wv][lane] = in;
+    s_pre[wv][lane] = incl - cnt;
+    s_seg[wv][lane] = in ? find_seg_by_line(g.a.segout, g.a.nsegs, l0) : 0u;
+    if (lane == 0) s_tot[wv] = total;
+    __syncthreads();
+    uint64_t base = g.cbase[c];
+    for (int k = 0; k < wv; ++k) base += s_tot[k];
+    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
+    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
+      const uint32_t k = k0 + (uint32_t)lane;
+      if (k >= total) continue;
+      uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
+#pragma unroll
+      for (uint32_t step = 32; step >= 1; step >>= 1)
+        if (s_pre[wv][j + step] <= k) j += step;
+      const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
+      const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
+      uint32_t s = s_seg[wv][j];
+      while (l >= g.a.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
+      const SegDesc sd = g.a.segs[s];
+      int64_t sec;
+      int32_t nsec;
+      tl_instant(g.a.bytes + sd.base, g.a.line_off[l + s], sd.len, sec, nsec);
+      const uint64_t ord = base + k;
+      if (ord < g.n) {  // (always: n is the scan's total of the same words)
+        g.items[0][ord] = TlItem{(uint64_t)sec ^ (1ull << 63), (uint32_t)nsec, (uint32_t)ord};
+        g.side[ord] = TlSide{l, s, 0u};
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t tl_digit(const TlItem& it, uint32_t p) {
+  return p < 4 ? (it.nsec >> (8 * p)) & 255u : (uint32_t)(it.sec_key >> (8 * (p - 4))) & 255u;
+}
+
+// One count into an LDS histogram per lane with `valid`; a wave whose lanes all hold the same
+// digit (the upper bytes of sec; a stream's lines of one second) adds once.  Every lane of the
+// wave calls it.
+__device__ __forceinline__ void tl_hist_add(uint32_t* h, uint32_t d, bool valid, int lane) {
+  const uint64_t act = __ballot(valid);
+  if (!act) return;
+  const int src = __ffsll((long long)act) - 1;
+  const uint32_t first = (uint32_t)__shfl((int)d, src, 64);
+  if (__all(!valid || d == first)) {
+    if (lane == src) atomicAdd(&h[first], (uint32_t)__popcll(act));
+  } else if (valid) {
+    atomicAdd(&h[d], 1u);
+  }
+}
+
+// All twelve digit histograms in one read of the items.
+__global__ __launch_bounds__(256) void k_tl_digits(const TlItem* __restrict__ items, uint64_t n,
+                                                   uint64_t* __restrict__ dhist) {
+  __shared__ uint32_t s_h[kTlDigits * 256];
+  const int t = threadIdx.x, lane = t & 63;
+  for (uint32_t k = t; k < kTlDigits * 256; k += 256) s_h[k] = 0;
+  __syncthreads();
+  for (uint64_t i0 = (uint64_t)blockIdx.x * 256; i0 < n; i0 += (uint64_t)gridDim.x * 256) {
+    const uint64_t i = i0 + t;
+    const bool valid = i < n;
+    TlItem it{};
+    if (valid) it = items[i];
+#pragma unroll
+    for (uint32_t p = 0; p < kTlDigits; ++p) tl_hist_add(s_h + p * 256, tl_digit(it, p), valid, lane);
+  }
+  __syncthreads();
+  for (uint32_t k = t; k < kTlDigits * 256; k += 256)
+    if (s_h[k]) atomicAdd(reinterpret_cast<unsigned long long*>(dhist + k), (unsigned long long)s_h[k]);
+}
+
+// One radix pass, 1: the digit counts of block b's kTlSortBlock items -> bcnt[d * nb + b].
+__global__ __launch_bounds__(256) void k_tl_bcount(const TlItem* __restrict__ items, uint64_t n, uint32_t p,
+                                                   uint32_t* __restrict__ bcnt, uint32_t nb) {
+  __shared__ uint32_t s_h[256];
+  const int t = threadIdx.x, lane = t & 63;
+  s_h[t] = 0;
+  __syncthreads();
+  const uint64_t i0 = (uint64_t)blockIdx.x * kTlSortBlock;
+  for (uint32_t r = 0; r < kTlSortBlock / 256; ++r) {
+    const uint64_t i = i0 + r * 256 + t;
+    const bool valid = i < n;
+    TlItem it{};
+    if (valid) it = items[i];
+    tl_hist_add(s_h, tl_digit(it, p), valid, lane);
+  }
+  __syncthreads();
+  bcnt[(size_t)t * nb + blockIdx.x] = s_h[t];
+}
+
+// 2: block d turns digit d's row of block counts into the blocks' first output positions: the
+// items of smaller digits (the digit histogram k_tl_digits made) + the row's exclusive prefix.
+__global__ __launch_bounds__(256) void k_tl_bscan(uint32_t* __restrict__ bcnt, uint32_t nb,
+                                                  const uint64_t* __restrict__ dh) {
+  __shared__ uint64_t s_w64[4];
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x;
+  const uint32_t d = blockIdx.x;
+  uint32_t carry = (uint32_t)block_sum_u64((uint32_t)t < d ? dh[t] : 0ull, s_w64);  // (< n < 2^32)
+  uint32_t* row = bcnt + (size_t)d * nb;
+  for (uint32_t b0 = 0; b0 < nb; b0 += 256) {
+    const uint32_t i = b0 + t;
+    const uint32_t x = i < nb ? row[i] : 0u;
+    uint32_t tot;
+    const uint32_t incl = block_incl_scan_u32(x, s_w, &tot);
+    if (i < nb) row[i] = carry + incl - x;
+    carry += tot;
+  }
+}
+
+// 3: the stable scatter.  Rounds of 256 items in order; within a round an item's place among
+// those of its digit = the round's items of earlier waves (per-wave LDS counts, prefixed in wave
+// order) + the earlier lanes of its own wave (the peer mask of 8 ballots).
+__global__ __launch_bounds__(256) void k_tl_scatter(const TlItem* __restrict__ src, TlItem* __restrict__ dst,
+                                                    uint64_t n, uint32_t p, const uint32_t* __restrict__ bcnt,
+                                                    uint32_t nb) {
+  __shared__ uint32_t s_base[256], s_wc[4][256];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  s_base[t] = bcnt[(size_t)t * nb + blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s_wc[k][t] = 0;
+  __syncthreads();
+  const uint64_t i0 = (uint64_t)blockIdx.x * kTlSortBlock;
+  for (uint32_t r = 0; r < kTlSortBlock / 256; ++r) {
+    const uint64_t i = i0 + r * 256 + t;
+    const bool valid = i < n;
+    TlItem it{};
+    if (valid) it = src[i];
+    const uint32_t d = tl_digit(it, p);
+    uint64_t peers = __ballot(valid);
+#pragma unroll
+    for (uint32_t bit = 0; bit < 8; ++bit) {
+      const bool on = (d >> bit) & 1u;
+      const uint64_t bal = __ballot(valid && on);
+      peers &= on ? bal : ~bal;
+    }
+    const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+    if (valid && rank == 0) s_wc[wv][d] = (uint32_t)__popcll(peers);
+    __syncthreads();
+    if (valid) {
+      uint32_t pos = s_base[d] + rank;
+      for (int k = 0; k < wv; ++k) pos += s_wc[k][d];
+      if (pos < n) dst[pos] = it;  // (always: the offsets partition [0, n))
+    }
+    __syncthreads();
+    s_base[t] += s_wc[0][t] + s_wc[1][t] + s_wc[2][t] + s_wc[3][t];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_wc[k][t] = 0;
+    __syncthreads();
+  }
+}
+
+// What the entry of one sorted item copies: `len` bytes from batch offset `src` behind its
+// stream's tag, and a '\n' when the line is its stream's unterminated fragment.
+struct TlGeom {
+  uint64_t src, line;
+  uint32_t len, seg, tag_off, tag_len, nl;
+};
+__device__ __forceinline__ TlGeom tl_geom(const TlArgs& g, const TlItem& it) {
+  TlGeom q{};
+  if (it.ord >= g.n) return q;  // (never: the sort permutes k_tl_keys' items)
+  const TlSide sd = g.side[it.ord];
+  const uint32_t s = sd.seg;
+  const uint64_t l = sd.line;
+  if (s >= g.a.nsegs || l >= g.a.cap_lines) return q;
+  const SegDesc seg = g.a.segs[s];
+  const uint64_t ls = g.a.line_off[l + s], le = g.a.line_off[l + s + 1];
+  const uint32_t plen = g.timestamps ? 0u : line_plen(g.a, g.a.meta[l], g.a.bytes + seg.base, ls, le);
+  q.src = seg.base + ls + plen;
+  q.len = (uint32_t)(le - ls - plen);
+  q.line = l - g.a.segout[s].line_lo;
+  q.seg = s;
+  q.tag_off = g.tags ? g.segtab[3 * s + 1] : 0u;
+  q.tag_len = g.tags ? g.segtab[3 * s + 2] : 0u;
+  q.nl = (le == seg.len && g.a.segout[s].frag) ? 1u : 0u;
+  return q;
+}
+
+__global__ __launch_bounds__(256) void k_tl_plan(TlArgs g, const TlItem* __restrict__ items) {
+  __shared__ uint64_t s_w64[4];
+  const uint64_t i = (uint64_t)blockIdx.x * kTlPlanBlock + threadIdx.x;
+  uint64_t len = 0;
+  if (i < g.n) {
+    const TlGeom q = tl_geom(g, items[i]);
+    len = (uint64_t)q.tag_len + q.len + q.nl;
+  }
+  len = block_sum_u64(len, s_w64);
+  if (threadIdx.x == 0) g.psum[blockIdx.x] = len;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64);
+  return (uint64_t)hi << 32 | lo;
+}
+
+// n bytes from src to dst over the wave's lanes: dwords at the destination's alignment (the
+// source dword through gword, which reads at most 4 bytes past the last one it needs), bytes
+// at both ends and for short copies.
+__device__ __forceinline__ void wave_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n,
+                                          int lane) {
+  uint32_t head = (uint32_t)(-reinterpret_cast<intptr_t>(dst)) & 3u;
+  if (n < 128 || head > n) head = n;
+  for (uint32_t k = lane; k < head; k += 64) dst[k] = src[k];
+  const uint32_t nd = (n - head) >> 2;
+  uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + head);
+  for (uint32_t k = lane; k < nd; k += 64) d4[k] = gword(src + head + 4 * k);
+  for (uint32_t k = head + 4 * nd + lane; k < n; k += 64) dst[k] = src[k];
+}
+
+// Offsets (in-block scan + the block's base), the entry records, and the gather copy: a wave
+// renders its 64 entries one after the other, each spread over its lanes.
+__global__ __launch_bounds__(256) void k_tl_copy(TlArgs g, const TlItem* __restrict__ items) {
+  __shared__ uint64_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t i = (uint64_t)blockIdx.x * kTlPlanBlock + t;
+  TlGeom q{};
+  TlItem it{};
+  uint64_t len = 0;
+  if (i < g.n) {
+    it = items[i];
+    q = tl_geom(g, it);
+    len = (uint64_t)q.tag_len + q.len + q.nl;
+  }
+  const uint64_t incl = wave_incl_scan_add(len, lane);
+  if (lane == 63) s_w[wv] = incl;
+  __syncthreads();
+  uint64_t off = g.psum[blockIdx.x] + incl - len;
+  for (int k = 0; k < wv; ++k) off += s_w[k];
+  if (i < g.n)
+    g.entries[i] = TlEntry{(int64_t)(it.sec_key ^ (1ull << 63)), (int32_t)it.nsec, g.segtab[3 * q.seg], q.line, off};
+  const uint64_t w0 = (uint64_t)blockIdx.x * kTlPlanBlock + (uint64_t)wv * 64;
+  const uint32_t nv = w0 >= g.n ? 0u : (g.n - w0 < 64 ? (uint32_t)(g.n - w0) : 64u);  // (wave-uniform)
+  for (uint32_t j = 0; j < nv; ++j) {
+    const uint64_t o = shfl64(off, (int)j), src = shfl64(q.src, (int)j);
+    const uint32_t n = (uint32_t)__shfl((int)q.len, (int)j, 64), to = (uint32_t)__shfl((int)q.tag_off, (int)j, 64),
+                   tl = (uint32_t)__shfl((int)q.tag_len, (int)j, 64), nl = (uint32_t)__shfl((int)q.nl, (int)j, 64);
+    for (uint32_t k = lane; k < tl; k += 64) g.out[o + k] = g.tags[to + k];
+    wave_copy(g.out + o + tl, g.a.bytes + src, n, lane);
+    if (nl && lane == 0) g.out[o + tl + n] = (uint8_t)'\n';
+  }
+}
+
 // Zeroes the run's counters and per-stream records (one launch instead of memsets).
 __global__ __launch_bounds__(256) void k_init(RunArgs a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -5040,6 +5396,58 @@ hipError_t launch_hist(const HistArgs& g, hipStream_t st, hipEvent_t ev0, hipEve
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipEventRecord(ev1, st);
+}
+
+hipError_t launch_tl_count(const TlArgs& g, hipStream_t st, int num_cus) {
+  if (g.nchunks) {
+    const uint64_t gmax = (uint64_t)num_cus * 16;
+    hipLaunchKernelGGL(k_tl_count, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.nchunks);
+  return hipGetLastError();
+}
+
+hipError_t launch_tl_keys(const TlArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
+  if (e != hipSuccess) return e;
+  if (!g.n || !g.nchunks) return hipSuccess;
+  const uint64_t gmax = (uint64_t)num_cus * 16;
+  hipLaunchKernelGGL(k_tl_keys, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const uint64_t nb = (g.n + 255) / 256, dmax = (uint64_t)num_cus * 8;
+  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items[0], g.n, g.dhist);
+  return hipGetLastError();
+}
+
+hipError_t launch_tl_pass(const TlArgs& g, uint32_t digit, uint32_t from, hipStream_t st) {
+  const uint32_t nb = (uint32_t)((g.n + kTlSortBlock - 1) / kTlSortBlock);
+  if (!nb || digit >= kTlDigits) return hipSuccess;
+  hipError_t e;
+  hipLaunchKernelGGL(k_tl_bcount, dim3(nb), dim3(256), 0, st, g.items[from & 1], g.n, digit, g.bcnt, nb);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_bscan, dim3(256), dim3(256), 0, st, g.bcnt, nb, g.dhist + (size_t)digit * 256);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_scatter, dim3(nb), dim3(256), 0, st, g.items[from & 1], g.items[(from & 1) ^ 1], g.n, digit,
+                     g.bcnt, nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t st) {
+  const uint64_t nb = (g.n + kTlPlanBlock - 1) / kTlPlanBlock;
+  if (nb) {
+    hipLaunchKernelGGL(k_tl_plan, dim3((uint32_t)nb), dim3(256), 0, st, g, g.items[which & 1]);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.psum, nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_tl_copy(const TlArgs& g, uint32_t which, hipStream_t st) {
+  const uint64_t nb = (g.n + kTlPlanBlock - 1) / kTlPlanBlock;
+  if (!nb) return hipSuccess;
+  hipLaunchKernelGGL(k_tl_copy, dim3((uint32_t)nb), dim3(256), 0, st, g, g.items[which & 1]);
+  return hipGetLastError();
 }
 
 }  // namespace klf

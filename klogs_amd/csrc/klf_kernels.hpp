@@ -424,6 +424,64 @@ struct HistArgs {
   uint64_t* table;          // [nsegs * (n_buckets + 2)] per segment: the buckets, below, above (zeroed by launch_hist)
 };
 
+// Merged timeline of a finished run (klf_result_timeline, SPEC.md S4d): the emitted lines E of
+// all streams, sorted by (sec, nsec, stream, line) and rendered into one buffer.
+//   k_tl_count / k_tl_scan    E lines per kMatchChunk chunk, their exclusive prefix -> n
+//   k_tl_keys                 k_hist's walk over E: item[ord] = the line's instant, side[ord] =
+//                             its (line, segment); ord = its rank in (stream, line) order
+//   k_tl_digits               the twelve 256-bin histograms of the 96-bit key in one read
+//   k_tl_bcount / k_tl_bscan / k_tl_scatter   one stable LSD pass (8-bit digit) between the two
+//                             item buffers; the host skips a pass whose digit is the same in all
+//   k_tl_plan / k_tl_scan / k_tl_copy   rendered lengths per block of sorted positions, their
+//                             prefix, then the entry records and the gather copy
+// No kernel waits on another block: kernel boundaries are the only ordering.
+struct alignas(16) TlItem {  // 16 B: the sort key and the line's rank before the sort
+  uint64_t sec_key;   // ts.sec ^ 2^63 (unsigned order = signed order of sec)
+  uint32_t nsec;
+  uint32_t ord;
+};
+struct alignas(16) TlSide {  // 16 B, indexed by TlItem::ord
+  uint64_t line;      // global line index
+  uint32_t seg, _pad;
+};
+struct TlEntry {      // = klf_timeline_entry
+  int64_t sec;
+  int32_t nsec;
+  uint32_t stream;
+  uint64_t line, off;
+};
+static_assert(sizeof(TlItem) == 16 && sizeof(TlSide) == 16 && sizeof(TlEntry) == 32, "timeline records");
+constexpr uint32_t kTlDigits = 12;          // 8-bit digits of the key: nsec bytes 0..3, then sec_key bytes 0..7
+constexpr uint32_t kTlSortBlock = 2048;     // items per block of a radix pass (8 rounds of 256)
+constexpr uint32_t kTlPlanBlock = 256;      // sorted positions per block of the plan / copy
+struct TlArgs {
+  RunArgs a;                // the run (read only): meta, line_off, bytes, segs, segout, nsegs
+  const uint32_t* bits_in;  // the selection bitmap (M, G' or G''); null: every line (no patterns)
+  uint64_t nchunks;         // kMatchChunk chunks holding lines
+  uint32_t timestamps;      // render the line's prefix too
+  const uint32_t* segtab;   // [3 * nsegs] per segment: stream id, tag offset, tag length
+  const uint8_t* tags;      // the tag bytes (null: no tags, every length 0)
+  uint64_t* cbase;          // [nchunks + 1] E lines per chunk, then their exclusive prefix and n
+  uint64_t n;               // entries (known after k_tl_scan)
+  TlItem* items[2];         // [n] each: the ping-pong buffers of the sort
+  TlSide* side;             // [n]
+  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_tl_keys)
+  uint32_t* bcnt;           // [256 * ceil(n / kTlSortBlock)] digit-major per-block counts, then offsets
+  uint64_t* psum;           // [ceil(n / kTlPlanBlock) + 1] rendered bytes per block, then prefix and total
+  TlEntry* entries;         // [n]
+  uint8_t* out;             // the merged bytes
+};
+// k_tl_count + k_tl_scan: g.cbase[g.nchunks] = n afterwards.
+hipError_t launch_tl_count(const TlArgs& g, hipStream_t stream, int num_cus);
+// k_tl_keys into g.items[0] / g.side, then g.dhist (k_tl_digits).
+hipError_t launch_tl_keys(const TlArgs& g, hipStream_t stream, int num_cus);
+// One radix pass over digit `digit` from g.items[from] into g.items[from ^ 1].
+hipError_t launch_tl_pass(const TlArgs& g, uint32_t digit, uint32_t from, hipStream_t stream);
+// k_tl_plan + k_tl_scan over the sorted g.items[which]: g.psum[blocks] = the merged length.
+hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t stream);
+// k_tl_copy: g.entries and g.out from the sorted g.items[which] and the scanned g.psum.
+hipError_t launch_tl_copy(const TlArgs& g, uint32_t which, hipStream_t stream);
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]

@@ -3,6 +3,7 @@
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
 //                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
+//                [--merge [--merge-timestamps]]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
 //
 // -A / -B / -C N (lines of context after / before / around a matching line) and
@@ -18,6 +19,10 @@
 // lines of the selection (after the pattern, the context flags and the window; before --since
 // and --tail, SPEC.md S4c, klf_result_histogram) counted in buckets of WIDTH from --from (else
 // the --since instant; one of the two is needed) up to --until (else --now), at most 65536.
+//
+// --merge also writes <logpath>/merged.log: the emitted lines of all containers in one
+// chronological sequence (SPEC.md S4d, klf_result_timeline), each behind "<pod>/<container> ";
+// --merge-timestamps keeps each line's timestamp.  The per-container files stay as they are.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -75,6 +80,9 @@ void usage() {
                "                    per stream in buckets of WIDTH, a duration > 0, from --from (else the --since\n"
                "                    instant; one of them is needed) up to --until (else --now), at most 65536\n"
                "                    buckets; counted before --since / --tail apply)\n"
+               "                    [--merge [--merge-timestamps]]   (also writes <logpath>/merged.log: the emitted\n"
+               "                    lines of all containers by time, each behind \"<pod>/<container> \"; with their\n"
+               "                    timestamps)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -94,6 +102,7 @@ int main(int argc, char** argv) {
   bool from_set = false, until_set = false;  // --from / --until
   std::string hist_arg;
   bool hist_set = false;  // --histogram
+  bool merge = false, merge_ts = false;  // --merge, --merge-timestamps
   auto context = [&](const std::string& v) -> uint32_t {
     char* end = nullptr;
     const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
@@ -120,6 +129,8 @@ int main(int argc, char** argv) {
     else if (a == "--from") { from_arg = val(); from_set = true; }
     else if (a == "--until") { until_arg = val(); until_set = true; }
     else if (a == "--histogram") { hist_arg = val(); hist_set = true; }
+    else if (a == "--merge") merge = true;
+    else if (a == "--merge-timestamps") merge_ts = true;
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -136,6 +147,7 @@ int main(int argc, char** argv) {
   }
   if (manifest.empty()) usage();
   if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
+  if (merge_ts && !merge) usage();
   // --from / --until: an instant, or a duration before `now` (--now may follow them)
   klf_window_opts window{{KLF_TIME_MIN_SEC, 0, 0}, {KLF_TIME_MAX_SEC, 0, 0},
                          regroup.before, regroup.after, regroup.flags, 0};
@@ -317,6 +329,27 @@ int main(int argc, char** argv) {
           std::fprintf(hf, "%s\t%s\tabove\t%llu\n", pod, cname[i].c_str(), (unsigned long long)ho[2 * (size_t)i + 1]);
       }
       if (std::fclose(hf) != 0) panic_exit("close " + hpath);
+    }
+    if (merge) {  // the timeline of the result that gets written, beside the per-container files
+      std::string tags;
+      std::vector<uint32_t> tag_off(n + 1, 0);
+      for (uint32_t i = 0; i < n; ++i) {
+        std::string tag = pods[table[i].pod].name + "/" + cname[i];
+        if (tag.size() > KLF_TIMELINE_MAX_TAG - 1) tag.resize(KLF_TIMELINE_MAX_TAG - 1);
+        tags += tag + " ";
+        tag_off[i + 1] = (uint32_t)tags.size();
+      }
+      const klf_timeline_opts topts{(const uint8_t*)tags.data(), tag_off.data(), merge_ts ? KLF_TIMELINE_TIMESTAMPS : 0u, 0};
+      klf_timeline* tl = nullptr;
+      rc = klf_result_timeline(r, &topts, &tl);
+      if (rc != KLF_OK) panic_exit(std::string("klf_result_timeline: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      const std::string mpath = logpath + "/merged.log";
+      const int mfd = ::open(mpath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+      if (mfd < 0) panic_exit("create " + mpath);
+      rc = klf_timeline_write(tl, mfd, nullptr);
+      if (rc != KLF_OK) panic_exit(std::string("klf_timeline_write: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      if (::close(mfd) != 0) panic_exit("close " + mpath);
+      klf_timeline_free(tl);
     }
     // writeLogToDisk (:359-374): one klf_result_write over every stream's file (chunked,
     // double-buffered D2H from pinned memory), files closed afterwards

@@ -31,6 +31,8 @@ GO_ZERO_TIME = (-62135596800, 0)
 TIME_MIN_SEC = -(1 << 63)     # KLF_TIME_MIN_SEC: klf_window_opts.from.sec, open below
 TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, open above
 HIST_MAX_BUCKETS = 65536      # KLF_HIST_MAX_BUCKETS: klf_hist_opts.n_buckets at most
+TIMELINE_TIMESTAMPS = 1       # KLF_TIMELINE_TIMESTAMPS: render each line's prefix too
+TIMELINE_MAX_TAG = 1024       # KLF_TIMELINE_MAX_TAG: bytes of one stream's tag at most
 
 MODE_NAMES = {0: "none", 1: "never", 2: "all", 3: "literal1", 4: "general"}
 
@@ -69,6 +71,14 @@ class _WindowOpts(C.Structure):
 
 class _HistOpts(C.Structure):
     _fields_ = [("origin", _Time), ("width_ns", C.c_uint64), ("n_buckets", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _TimelineOpts(C.Structure):
+    _fields_ = [("tags", C.c_void_p), ("tag_off", C.c_void_p), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+# klf_timeline_entry (32 bytes)
+TIMELINE_ENTRY = np.dtype([("sec", "<i8"), ("nsec", "<i4"), ("stream", "<u4"), ("line", "<u8"), ("off", "<u8")])
 
 
 class _Counts(C.Structure):
@@ -114,6 +124,12 @@ SIGNATURES = {
     "klf_result_index_mode": (C.c_int, [C.c_void_p]),
     "klf_result_compaction": (C.c_int, [C.c_void_p]),
     "klf_result_free": (None, [C.c_void_p]),
+    "klf_result_timeline": (C.c_int, [C.c_void_p, C.POINTER(_TimelineOpts), C.POINTER(C.c_void_p)]),
+    "klf_timeline_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "klf_timeline_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "klf_timeline_write": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "klf_timeline_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "klf_timeline_free": (None, [C.c_void_p]),
     "klf_follow_open": (C.c_int, [C.c_void_p, C.POINTER(_Filter), C.POINTER(C.c_void_p)]),
     "klf_follow_feed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
     "klf_follow_flush": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -298,6 +314,58 @@ def debug_clock(device: int = 0, iters: int = 200_000, reps: int = 20):
     return {"median_mhz": round(out[0], 1), "min_mhz": round(out[1], 1), "max_mhz": round(out[2], 1)}
 
 
+class Timeline:
+    """A merged timeline (klf_timeline): `entries` is a numpy structured array (TIMELINE_ENTRY:
+    sec, nsec, stream, line, off), `bytes` the rendered entries in timeline order."""
+
+    def __init__(self, ptr: int, eng):
+        self._p = C.c_void_p(ptr)
+        self._eng = eng
+
+    @property
+    def entries(self) -> np.ndarray:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.klf_timeline_entries(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        if not n.value:
+            return np.zeros(0, dtype=TIMELINE_ENTRY)
+        return np.frombuffer(C.string_at(p.value, n.value * TIMELINE_ENTRY.itemsize), dtype=TIMELINE_ENTRY).copy()
+
+    def __len__(self) -> int:
+        n = C.c_uint64()
+        p = C.c_void_p()
+        _check(_lib.klf_timeline_entries(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        return int(n.value)
+
+    @property
+    def size(self) -> int:
+        """Length of the merged bytes (no copy)."""
+        n = C.c_uint64()
+        _check(_lib.klf_timeline_bytes(self._p, None, C.byref(n)), self._eng._h)
+        return int(n.value)
+
+    @property
+    def bytes(self) -> bytes:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.klf_timeline_bytes(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def write(self, fd: int) -> int:
+        w = C.c_uint64()
+        _check(_lib.klf_timeline_write(self._p, int(fd), C.byref(w)), self._eng._h)
+        return int(w.value)
+
+    @property
+    def ms(self) -> float:
+        v = C.c_double()
+        _check(_lib.klf_timeline_ms(self._p, C.byref(v)), self._eng._h)
+        return float(v.value)
+
+    def free(self):
+        if self._p:
+            _lib.klf_timeline_free(self._p)
+            self._p = C.c_void_p()
+
+
 @dataclass
 class StreamOut:
     out: bytes
@@ -375,6 +443,29 @@ class Result:
                                          C.c_void_p(outside.ctypes.data), C.byref(ms)), self._eng._h)
         self.hist_ms = float(ms.value)
         return counts[: self.n_streams], outside[: self.n_streams]
+
+    def timeline(self, tags: Optional[Sequence[bytes]] = None, timestamps: bool = False) -> "Timeline":
+        """klf_result_timeline (SPEC.md S4d): the emitted lines of all streams in one sequence
+        ordered by (instant, stream, line).  tags: one byte string per stream, put in front of
+        each of its entries (None: no tags); timestamps: keep each line's timestamp prefix.
+        Read-only: this result stays the latest and valid.  The Timeline owns its buffers: it
+        outlives later runs and must be freed before the engine is closed."""
+        o = _TimelineOpts()
+        keep = None
+        if tags is not None:
+            tags = [bytes(x) for x in tags]
+            if len(tags) != self.n_streams:
+                raise ValueError(f"timeline: {len(tags)} tags for {self.n_streams} streams")
+            blob = np.frombuffer(b"".join(tags) + b"\0", dtype=np.uint8).copy()
+            off = np.zeros(self.n_streams + 1, dtype=np.uint32)
+            np.cumsum([len(x) for x in tags], out=off[1:])
+            o.tags, o.tag_off = blob.ctypes.data, off.ctypes.data
+            keep = (blob, off)
+        o.flags = TIMELINE_TIMESTAMPS if timestamps else 0
+        p = C.c_void_p()
+        _check(_lib.klf_result_timeline(self._p, C.byref(o), C.byref(p)), self._eng._h)
+        del keep
+        return Timeline(p.value, self._eng)
 
     def last_unparsed(self, i: int) -> int:
         """klf_result_last_unparsed: rank from the end (over newline-terminated lines) of the
