@@ -1771,10 +1771,27 @@ static int ensure_index(klf_engine* e);
 static bool window_closed(const klf_window_opts* tw) {
   return tw->from.sec != KLF_TIME_MIN_SEC || tw->until.sec != KLF_TIME_MAX_SEC;
 }
+// Transforms and accessors of a finished run read the engine's workspace: only the latest
+// result still owns it.
+static int check_latest(klf_engine* e, const klf_result* r, const char* what) {
+  if (r->gen != e->gen || e->last_gen != r->gen) return set_err(e, KLF_ESTATE, std::string(what) + ": not the latest run");
+  return KLF_OK;
+}
+// The bitmap r was selected from (klf_result_group_bits): G' / G'', M, or none (no patterns:
+// the parsed lines).
+static const uint32_t* sel_bits(const klf_result* r) {
+  return r->grouped ? r->e->d_gbits.as<uint32_t>() : r->has_bits ? r->e->d_bits.as<uint32_t>() : nullptr;
+}
+// What the kernels over r's selected lines read of its run (e->last_args: r is the latest).
+static klf::SelView sel_view(const klf_result* r) {
+  const klf::RunArgs& a = r->e->last_args;
+  const uint64_t nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;  // (<= cap_lines / kMatchChunk + 1)
+  return {sel_bits(r), a.meta, a.line_off, a.bytes, a.segs, a.segout, (uint32_t)r->so.size(), a.cap_lines, nchunks};
+}
+
 static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
                        const char* what, const klf_window_opts* tw = nullptr) {
-  if (prev->gen != e->gen || e->last_gen != prev->gen)
-    return set_err(e, KLF_ESTATE, std::string(what) + ": not the latest run");
+  if (int rc = check_latest(e, prev, what)) return rc;
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   auto* r = new (std::nothrow) klf_result();
@@ -1813,31 +1830,20 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
       const uint64_t nw = a.cap_lines / 32 + 1, nc = a.cap_lines / klf::kMatchChunk + 1;
       h = e->d_gbits.ensure(nw * 4);
       if (h == hipSuccess) h = e->d_gsum.ensure(nc * 4 * 8);
-      g.bits_in = e->d_bits.as<uint32_t>();
+      g.v = sel_view(prev);
+      g.v.bits_in = a.bits;  // M
       g.bits_out = e->d_gbits.as<uint32_t>();
-      g.meta = a.meta;
-      g.segout = a.segout;
-      g.nsegs = nsegs;
       g.invert = (o->flags & KLF_REGROUP_INVERT) ? 1u : 0u;
-      g.cap_lines = a.cap_lines;
       g.before = o->before;
       g.after = o->after;
-      g.csum = e->d_gsum.as<uint64_t>();
-      g.nchunks = (prev->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;  // (<= nc: lines <= cap_lines)
+      g.csum = e->d_gsum.as<uint64_t>();  // (nc >= g.v.nchunks chunks)
       a.bits = g.bits_out;
     }
     if (cut) {
       if (h == hipSuccess) h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
-      wa.bits_in = prev->has_bits ? a.bits : nullptr;  // G' (d_gbits, in place), M, or the parsed lines
+      wa.v = sel_view(prev);
+      wa.v.bits_in = prev->has_bits ? a.bits : nullptr;  // G' (d_gbits, in place), M, or the parsed lines
       wa.bits_out = e->d_gbits.as<uint32_t>();
-      wa.meta = a.meta;
-      wa.line_off = a.line_off;
-      wa.bytes = a.bytes;
-      wa.segs = a.segs;
-      wa.segout = a.segout;
-      wa.nsegs = nsegs;
-      wa.cap_lines = a.cap_lines;
-      wa.nchunks = (prev->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
       wa.from_sec = tw->from.sec;
       wa.from_nsec = tw->from.nsec;
       wa.until_sec = tw->until.sec;
@@ -2210,12 +2216,13 @@ extern "C" int klf_result_lines(klf_result* r, uint32_t id, const uint64_t** off
   return KLF_OK;
 }
 
-// The per-stream packing of one of the run's line bitmaps: which = 0 the match bitmap M
-// (d_bits), 1 a regrouped result's selection bitmap G' (d_gbits).
-static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes, int which) {
+// The per-stream packing of one of the run's line bitmaps: the match bitmap M (d_bits) or,
+// with `group`, the bitmap r was selected from (sel_bits: a regrouped result's G' in d_gbits).
+static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes, bool group) {
   int rc = check_result(r, id);
   if (rc) return rc;
-  if (!r->has_bits && !(which && r->grouped)) return KLF_EINVAL;  // (no patterns: a window's G'' only)
+  const int which = group && r->grouped ? 1 : 0;
+  if (!r->has_bits && !which) return KLF_EINVAL;  // (no patterns: a window's G'' only)
   klf_engine* e = r->e;
   auto& hb = r->hbits[which];
   if (!hb.have) {
@@ -2223,7 +2230,7 @@ static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_
     const size_t nw = r->total_lines / 32 + 1;
     hb.bits.assign(nw, 0);
     if (!r->so.empty()) {
-      const void* src = which ? e->d_gbits.p : e->d_bits.p;
+      const void* src = group ? sel_bits(r) : e->d_bits.p;
       HIPCHK(e, hipMemcpyAsync(hb.bits.data(), src, nw * 4, hipMemcpyDeviceToHost, e->stream), "D2H bits");
       HIPCHK(e, hipStreamSynchronize(e->stream), "sync");
     }
@@ -2250,11 +2257,11 @@ static int result_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_
 }
 
 extern "C" int klf_result_match_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes) {
-  return result_bits(r, id, bits, nbytes, 0);
+  return result_bits(r, id, bits, nbytes, false);
 }
 
 extern "C" int klf_result_group_bits(klf_result* r, uint32_t id, const uint8_t** bits, uint64_t* nbytes) {
-  return result_bits(r, id, bits, nbytes, r && r->grouped ? 1 : 0);
+  return result_bits(r, id, bits, nbytes, true);
 }
 
 extern "C" int klf_result_pattern_counts(klf_result* r, uint32_t id, uint64_t* counts, uint32_t cap, uint32_t* n) {
@@ -2294,8 +2301,7 @@ extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint6
     return set_err(e, KLF_EINVAL, "klf_result_histogram: nsec outside [0, 1e9)");
   if (o->flags || o->origin._reserved)
     return set_err(e, KLF_EINVAL, "klf_result_histogram: unknown flag bits or a non-zero _reserved");
-  if (r->gen != e->gen || e->last_gen != r->gen)
-    return set_err(e, KLF_ESTATE, "klf_result_histogram: not the latest run");
+  if (int rc = check_latest(e, r, "klf_result_histogram")) return rc;
   const uint32_t nsegs = (uint32_t)r->so.size(), nb = o->n_buckets;
   const uint64_t row = (uint64_t)nb + 2;
   if ((uint64_t)nsegs * row > (1ull << 24))
@@ -2306,20 +2312,10 @@ extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint6
   if (!nsegs) return KLF_OK;
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  const klf::RunArgs& a = e->last_args;
   const uint64_t span = o->width_ns * nb;  // ns, < 2^63
   klf::HistArgs g{};
-  // the bitmap r was selected from (klf_result_group_bits): G' / G'', M, or the parsed lines
-  g.bits_in = r->grouped ? e->d_gbits.as<uint32_t>() : r->has_bits ? e->d_bits.as<uint32_t>() : nullptr;
-  g.meta = a.meta;
-  g.line_off = a.line_off;
-  g.bytes = a.bytes;
-  g.segs = a.segs;
-  g.segout = a.segout;
-  g.nsegs = nsegs;
+  g.v = sel_view(r);
   g.n_buckets = nb;
-  g.cap_lines = a.cap_lines;
-  g.nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
   g.org_sec = o->origin.sec;
   g.org_nsec = o->origin.nsec;
   int64_t end_nsec = o->origin.nsec + (int64_t)(span % 1000000000ull), carry = 0;
@@ -2407,8 +2403,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
       if (o->tag_off[i + 1] - o->tag_off[i] > KLF_TIMELINE_MAX_TAG)
         return set_err(e, KLF_EINVAL, "klf_result_timeline: a tag is longer than KLF_TIMELINE_MAX_TAG");
     }
-  if (r->gen != e->gen || e->last_gen != r->gen)
-    return set_err(e, KLF_ESTATE, "klf_result_timeline: not the latest run");
+  if (int rc = check_latest(e, r, "klf_result_timeline")) return rc;
   std::unique_ptr<klf_timeline> t(new (std::nothrow) klf_timeline());
   if (!t) return KLF_ENOMEM;
   t->e = e;
@@ -2422,10 +2417,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
   hipStream_t st = e->stream;
   TlScratch sc;
   klf::TlArgs g{};
-  g.a = e->last_args;
-  // the bitmap r was selected over (klf_result_group_bits): G' / G'', M, or every line
-  g.bits_in = r->grouped ? e->d_gbits.as<uint32_t>() : r->has_bits ? e->d_bits.as<uint32_t>() : nullptr;
-  g.nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;
+  g.v = sel_view(r);
   g.timestamps = (o->flags & KLF_TIMELINE_TIMESTAMPS) ? 1u : 0u;
   // per segment: its stream id and its tag
   std::vector<uint32_t> segtab((size_t)nsegs * 3, 0u);
@@ -2447,7 +2439,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
     HIPCHK(e, hipMemcpyAsync(sc.tags.p, o->tags, tag_bytes, hipMemcpyHostToDevice, st), "H2D tags");
     g.tags = sc.tags.as<uint8_t>();
   }
-  if (int rc = tl_alloc(e, sc.cbase, (g.nchunks + 1) * 8, "chunk bases")) return rc;
+  if (int rc = tl_alloc(e, sc.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
   g.cbase = sc.cbase.as<uint64_t>();
   for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "timeline events");
   auto finish = [&]() -> int {  // the device time, first launch to last
@@ -2462,7 +2454,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
   // 1. E lines per chunk -> n
   HIPCHK(e, klf::launch_tl_count(g, st, e->num_cus), "launch k_tl_count");
   uint64_t n = 0;
-  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H timeline size");
+  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H timeline size");
   HIPCHK(e, hipStreamSynchronize(st), "sync timeline size");
   if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_timeline: more than 2^32 - 1 entries");
   if (!n) {

@@ -1953,7 +1953,8 @@ __device__ bool rx_match(const DevPatterns& P, uint32_t r, const uint8_t* p, int
   return (d & P.rx_end[r]) != 0;
 }
 
-__device__ __forceinline__ uint32_t line_plen(const RunArgs& a, uint16_t meta, const uint8_t* segp,
+template <class Args>  // (unread: RunArgs for the run's kernels, TlArgs for the timeline's)
+__device__ __forceinline__ uint32_t line_plen(const Args& a, uint16_t meta, const uint8_t* segp,
                                               uint64_t start, uint64_t end) {
   uint32_t plen = meta >> 2;
   if (plen == kPlenEscape) {  // long prefix: find the first space again
@@ -2852,9 +2853,10 @@ __device__ __forceinline__ void block_excl_scan_max64(uint64_t x, uint64_t y, ui
   *post = re;
 }
 
-// The parsed bits of word w's 32 lines (16-B loads of their meta; line by line where the
-// word reaches past the line count).
-__device__ __forceinline__ uint32_t parsed_word(const uint16_t* __restrict__ meta, uint64_t w, uint64_t L) {
+// The parsed bits of word w's 32 lines, or with SINCE their parsed-and-since_ok bits (16-B
+// loads of their meta; line by line where the word reaches past the line count).
+template <bool SINCE>
+__device__ __forceinline__ uint32_t meta_word(const uint16_t* __restrict__ meta, uint64_t w, uint64_t L) {
   const uint64_t l0 = w * 32;
   uint32_t p = 0;
   if (l0 + 32 <= L) {
@@ -2864,19 +2866,35 @@ __device__ __forceinline__ uint32_t parsed_word(const uint16_t* __restrict__ met
       const uint4 v = q[k];
       const uint32_t x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        p |= ((x[j] & 1u) | ((x[j] >> 15) & 2u)) << (8 * k + 2 * j);
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t y = SINCE ? x[j] & (x[j] >> 1) : x[j];  // bit 0 / bit 16: the low / high line's flag(s)
+        p |= ((y & 1u) | ((y >> 15) & 2u)) << (8 * k + 2 * j);
+      }
     }
   } else {
-    for (uint64_t l = l0; l < L; ++l) p |= (uint32_t)(meta[l] & Meta::kParsed) << (l - l0);
+    for (uint64_t l = l0; l < L; ++l) {
+      const uint32_t m = meta[l];
+      p |= ((SINCE ? m & (m >> 1) : m) & Meta::kParsed) << (l - l0);
+    }
   }
   return p;
 }
-// Word w of S (0 past the line count).
-__device__ __forceinline__ uint32_t rg_s_word(const RegroupArgs& g, uint64_t w, uint64_t L) {
+// Word w of the view's selection (0 past the line count): its bitmap, or without one the
+// parsed lines.
+__device__ __forceinline__ uint32_t view_word(const SelView& v, uint64_t w, uint64_t L) {
   if (w * 32 >= L) return 0u;
-  const uint32_t m = g.bits_in[w] & word_range_mask(w, 0, L);
-  return g.invert ? parsed_word(g.meta, w, L) & ~m : m;
+  return v.bits_in ? v.bits_in[w] & word_range_mask(w, 0, L) : meta_word<false>(v.meta, w, L);
+}
+// Word w of S (0 past the line count).  pw (nullable): the word's parsed bits as well; without
+// it the meta is read only when S is inverted.
+__device__ __forceinline__ uint32_t rg_s_word(const RegroupArgs& g, uint64_t w, uint64_t L, uint32_t* pw = nullptr) {
+  if (pw) *pw = 0u;
+  if (w * 32 >= L) return 0u;
+  const uint32_t m = g.v.bits_in[w] & word_range_mask(w, 0, L);
+  if (!pw && !g.invert) return m;
+  const uint32_t p = meta_word<false>(g.v.meta, w, L);
+  if (pw) *pw = p;
+  return g.invert ? p & ~m : m;
 }
 // x | x << 1 | ... | x << k (UP) or the same with right shifts, k <= 31: doubling steps.
 template <bool UP>
@@ -2893,8 +2911,8 @@ __device__ __forceinline__ uint32_t smear(uint32_t x, uint32_t k) {
 __global__ __launch_bounds__(256) void k_rg_sum(RegroupArgs g) {
   __shared__ uint64_t s_w[2][4];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t;
     const uint32_t s = rg_s_word(g, w, L);
     uint64_t last = s ? w * 32 + (31 - __clz(s)) + 1 : 0, first = s ? ~(w * 32 + (__ffs(s) - 1)) : 0;
@@ -2923,8 +2941,8 @@ __global__ __launch_bounds__(256) void k_rg_sum(RegroupArgs g) {
 // exclusive prefix / suffix.
 __global__ __launch_bounds__(256) void k_rg_carry(RegroupArgs g) {
   __shared__ uint64_t s_w[2][4];
-  const uint64_t K = (g.nchunks + 255) / 256;
-  const uint64_t c0 = threadIdx.x * K, c1 = c0 + K < g.nchunks ? c0 + K : g.nchunks;
+  const uint64_t K = (g.v.nchunks + 255) / 256;
+  const uint64_t c0 = threadIdx.x * K, c1 = c0 + K < g.v.nchunks ? c0 + K : g.v.nchunks;
   uint64_t a = 0, b = 0;
   for (uint64_t c = c0; c < c1; ++c) {
     const uint64_t x = g.csum[4 * c], y = g.csum[4 * c + 1];
@@ -2948,28 +2966,23 @@ __global__ __launch_bounds__(256) void k_rg_carry(RegroupArgs g) {
 __global__ __launch_bounds__(256) void k_rg_build(RegroupArgs g) {
   __shared__ uint64_t s_w[2][4];
   const int t = threadIdx.x;
-  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
-  const uint64_t nw = g.cap_lines / 32 + 1;  // words of the bitmaps
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  const uint64_t nw = g.v.cap_lines / 32 + 1;  // words of the bitmaps
   const uint32_t ka = g.after < 31 ? (uint32_t)g.after : 31u, kb = g.before < 31 ? (uint32_t)g.before : 31u;
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    const bool live = l0 < L;
-    uint32_t pw = 0, sw = 0;
-    if (live) {
-      pw = parsed_word(g.meta, w, L);
-      const uint32_t m = g.bits_in[w] & word_range_mask(w, 0, L);
-      sw = g.invert ? pw & ~m : m;
-    }
+    uint32_t pw;  // (0 past the line count, no bit at or past L)
+    const uint32_t sw = rg_s_word(g, w, L, &pw);
     uint64_t pk, nk;  // P + 1 over the words before this one, ~N over the words after it
     block_excl_scan_max64(sw ? l0 + (31 - __clz(sw)) + 1 : 0, sw ? ~(l0 + (__ffs(sw) - 1)) : 0, s_w, &pk, &nk);
     const uint64_t cp = g.csum[4 * c + 2], cn = g.csum[4 * c + 3];
     pk = pk > cp ? pk : cp;
     nk = nk > cn ? nk : cn;
     uint32_t out = 0;
-    if (live && pw) {
+    if (pw) {
       const uint64_t wend = l0 + 32;
-      for (uint32_t s = find_seg_by_line(g.segout, g.nsegs, l0); s < g.nsegs; ++s) {
-        const uint64_t lo = g.segout[s].line_lo, hi = g.segout[s].line_hi;
+      for (uint32_t s = find_seg_by_line(g.v.segout, g.v.nsegs, l0); s < g.v.nsegs; ++s) {
+        const uint64_t lo = g.v.segout[s].line_lo, hi = g.v.segout[s].line_hi;
         if (lo >= wend) break;
         const uint32_t pm = word_range_mask(w, lo, hi);
         const uint32_t sp = sw & pm;
@@ -3054,45 +3067,80 @@ __device__ __forceinline__ uint32_t nth_set_bit(uint32_t w, uint32_t n) {
   return pos;
 }
 
-// A wave shares the lines of its 64 words over its lanes (LDS: the words, the exclusive
-// prefix of their popcounts, each word's first stream): lane i of round r takes the wave's
-// (64 r + i)-th line of G', so a round reads 64 consecutive lines of G' -- consecutive index
-// entries and, where G' is dense, neighbouring bytes of the batch.  One thread per word walking
-// its own 32 lines took 2.13 ms on the C3 shape (55.6 M lines, all in G'); see DESIGN.md.
+// The selected-line walk (k_tw_build, k_hist, k_tl_keys): one block per kMatchChunk lines, one
+// thread per bitmap word `in` of the selection (no bit at or past the line count L).  A wave
+// shares the lines of its 64 words over its lanes (LDS: the words, the exclusive prefix of
+// their popcounts, each word's first stream): lane i of round r takes the wave's (64 r + i)-th
+// selected line, so a round reads 64 consecutive selected lines -- consecutive index entries
+// and, where the selection is dense, neighbouring bytes of the batch.  One thread per word
+// walking its own 32 lines took 2.13 ms on the C3 shape (55.6 M lines, all selected); see
+// DESIGN.md.  Per chunk: walk_publish, the kernel's own LDS stores, __syncthreads(),
+// walk_rounds.
+struct WalkLds {
+  uint32_t in[4][64], pre[4][64], seg[4][64];
+};
+// Publishes the thread's word (first line l0) behind a barrier that ends the previous chunk's
+// LDS reads; returns the wave's selected lines (wave-uniform).  The caller's barrier follows.
+__device__ __forceinline__ uint32_t walk_publish(WalkLds& ws, const SelView& v, uint32_t in, uint64_t l0) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t cnt = (uint32_t)__popc(in);
+  const uint32_t incl = wave_incl_scan_add(cnt, lane);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  __syncthreads();
+  ws.in[wv][lane] = in;
+  ws.pre[wv][lane] = incl - cnt;
+  ws.seg[wv][lane] = in ? find_seg_by_line(v.segout, v.nsegs, l0) : 0u;
+  return total;
+}
+// One selected line of a round: the wave's k-th, bit b of the wave's word j, global line l of
+// segment s at stream offset off.  live false: the lane has no line this round; k alone is set.
+struct WalkLine {
+  bool live;
+  uint32_t k, j, b, s;
+  uint64_t l, off;
+  SegDesc sd;
+};
+// The rounds: f(const WalkLine&) on every lane of every round (total is wave-uniform), so f may
+// use cross-lane operations.
+template <class F>
+__device__ __forceinline__ void walk_rounds(const WalkLds& ws, const SelView& v, uint32_t total, uint64_t l0, F&& f) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
+  for (uint32_t k0 = 0; k0 < total; k0 += 64) {
+    WalkLine q;  // (the rest stays unset on a lane without a line: nothing to merge after the branch)
+    q.k = k0 + (uint32_t)lane;
+    q.live = q.k < total;
+    if (q.live) {
+      uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
+#pragma unroll
+      for (uint32_t step = 32; step >= 1; step >>= 1)
+        if (ws.pre[wv][j + step] <= q.k) j += step;
+      q.j = j;
+      q.b = nth_set_bit(ws.in[wv][j], q.k - ws.pre[wv][j]);
+      q.l = wl0 + (uint64_t)j * 32 + q.b;  // (< L: `in` has no bit at or past L)
+      q.s = ws.seg[wv][j];
+      while (q.l >= v.segout[q.s].line_hi) ++q.s;  // (a word may span streams; s stays < nsegs as l < L)
+      q.sd = v.segs[q.s];
+      q.off = v.line_off[q.l + q.s];
+    }
+    f(q);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_tw_build(WindowArgs g) {
-  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64], s_out[4][64];
+  __shared__ WalkLds ws;
+  __shared__ uint32_t s_out[4][64];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
-  const uint64_t nw = g.cap_lines / 32 + 1;  // words of the bitmaps
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  const uint64_t nw = g.v.cap_lines / 32 + 1;  // words of the bitmaps
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    uint32_t in = 0;
-    if (l0 < L) in = g.bits_in ? g.bits_in[w] & word_range_mask(w, 0, L) : parsed_word(g.meta, w, L);
-    const uint32_t cnt = (uint32_t)__popc(in);
-    const uint32_t incl = wave_incl_scan_add(cnt, lane);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of G'
-    __syncthreads();  // (the previous chunk's s_out is read)
-    s_in[wv][lane] = in;
-    s_pre[wv][lane] = incl - cnt;
-    s_seg[wv][lane] = in ? find_seg_by_line(g.segout, g.nsegs, l0) : 0u;
+    const uint32_t total = walk_publish(ws, g.v, view_word(g.v, w, L), l0);  // (the previous chunk's s_out is read)
     s_out[wv][lane] = 0u;
     __syncthreads();
-    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
-    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
-      const uint32_t k = k0 + (uint32_t)lane;
-      if (k < total) {
-        uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
-#pragma unroll
-        for (uint32_t step = 32; step >= 1; step >>= 1)
-          if (s_pre[wv][j + step] <= k) j += step;
-        const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
-        const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
-        uint32_t s = s_seg[wv][j];
-        while (l >= g.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
-        const SegDesc sd = g.segs[s];
-        if (tw_line_in(g, g.bytes + sd.base, g.line_off[l + s], sd.len)) atomicOr(&s_out[wv][j], 1u << b);
-      }
-    }
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
+      if (q.live && tw_line_in(g, g.v.bytes + q.sd.base, q.off, q.sd.len)) atomicOr(&s_out[wv][q.j], 1u << q.b);
+    });
     __syncthreads();
     if (w < nw) g.bits_out[w] = s_out[wv][lane];
   }
@@ -3101,8 +3149,8 @@ __global__ __launch_bounds__(256) void k_tw_build(WindowArgs g) {
 // ====================================== histogram over time (klf_result_histogram, SPEC.md S4c) ==
 // Per stream, the lines of a selection bitmap H counted by instant: below `origin`, in one of
 // n_buckets buckets of width_ns from `origin` on, or at / above `end` = origin + n_buckets *
-// width_ns.  The walk is k_tw_build's (lane i of round r takes the wave's (64 r + i)-th line of
-// H and reads the first 32 bytes of that line); in place of a bit per line each line gets a key
+// width_ns.  The selected-line walk over H (walk_publish / walk_rounds), reading the first 32
+// bytes of each line; in place of a bit per line each line gets a key
 // = segment * (n_buckets + 2) + slot (slot n_buckets = below, n_buckets + 1 = above) into the
 // u64 table.  The 64 consecutive lines of a round mostly share a key, so a lane adds only when
 // its key differs from the previous lane's, and adds the length of its run of equal keys (from
@@ -3119,21 +3167,29 @@ __device__ __forceinline__ void canon_instant(const uint32_t (&p)[6], int64_t& s
                    (p[5] & 15u));
 }
 
+// The instant of the line at segp + off: a canonical prefix from its packed digits, every
+// other shape through the general parser.  False (sec / nsec untouched): the line has none.
+__device__ __forceinline__ bool line_instant(const uint8_t* __restrict__ segp, uint64_t off, uint64_t seg_len,
+                                             int64_t& sec, int32_t& nsec) {
+  uint32_t p[6];
+  if (tw_canon_digits(segp, off, p)) {
+    canon_instant(p, sec, nsec);
+    return true;
+  }
+  TsResult r;
+  uint32_t plen;
+  if (!parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) return false;
+  sec = r.sec;
+  nsec = r.nsec;
+  return true;
+}
+
 // The table slot of the line at segp + off, or ~0u for a line without an instant (none in H).
 __device__ __forceinline__ uint32_t hist_slot(const HistArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
                                               uint64_t seg_len) {
-  uint32_t p[6];
   int64_t sec;
   int32_t nsec;
-  if (tw_canon_digits(segp, off, p)) {
-    canon_instant(p, sec, nsec);
-  } else {
-    TsResult r;
-    uint32_t plen;
-    if (!parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) return ~0u;
-    sec = r.sec;
-    nsec = r.nsec;
-  }
+  if (!line_instant(segp, off, seg_len, sec, nsec)) return ~0u;
   if (time_before(sec, nsec, g.org_sec, g.org_nsec)) return g.n_buckets;
   if (!g.end_open && !time_before(sec, nsec, g.end_sec, g.end_nsec)) return g.n_buckets + 1;
   // origin <= ts < end: d = ts - origin in ns lies in [0, n_buckets * width_ns), below 2^63
@@ -3145,38 +3201,19 @@ __device__ __forceinline__ uint32_t hist_slot(const HistArgs& g, const uint8_t* 
 }
 
 __global__ __launch_bounds__(256) void k_hist(HistArgs g) {
-  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.segout[g.nsegs - 1].line_hi;
+  __shared__ WalkLds ws;
+  const int t = threadIdx.x, lane = t & 63;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
   const uint32_t row = g.n_buckets + 2;
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    uint32_t in = 0;
-    if (l0 < L) in = g.bits_in ? g.bits_in[w] & word_range_mask(w, 0, L) : parsed_word(g.meta, w, L);
-    const uint32_t cnt = (uint32_t)__popc(in);
-    const uint32_t incl = wave_incl_scan_add(cnt, lane);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of H
-    __syncthreads();  // (the previous chunk's words are read)
-    s_in[wv][lane] = in;
-    s_pre[wv][lane] = incl - cnt;
-    s_seg[wv][lane] = in ? find_seg_by_line(g.segout, g.nsegs, l0) : 0u;
+    const uint32_t total = walk_publish(ws, g.v, view_word(g.v, w, L), l0);
     __syncthreads();
-    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
-    for (uint32_t k0 = 0; k0 < total; k0 += 64) {   // (total is wave-uniform: every lane takes every round)
-      const uint32_t k = k0 + (uint32_t)lane;
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
       uint32_t key = ~0u;  // no line, or a line without an instant
-      if (k < total) {
-        uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
-#pragma unroll
-        for (uint32_t step = 32; step >= 1; step >>= 1)
-          if (s_pre[wv][j + step] <= k) j += step;
-        const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
-        const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
-        uint32_t s = s_seg[wv][j];
-        while (l >= g.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
-        const SegDesc sd = g.segs[s];
-        const uint32_t slot = hist_slot(g, g.bytes + sd.base, g.line_off[l + s], sd.len);
-        if (slot < row) key = s * row + slot;  // (< nsegs * row <= 2^24: the host's size check)
+      if (q.live) {
+        const uint32_t slot = hist_slot(g, g.v.bytes + q.sd.base, q.off, q.sd.len);
+        if (slot < row) key = q.s * row + slot;  // (< nsegs * row <= 2^24: the host's size check)
       }
       const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
       const bool head = lane == 0 || key != prev;
@@ -3186,7 +3223,7 @@ __global__ __launch_bounds__(256) void k_hist(HistArgs g) {
         const uint32_t run = after ? (uint32_t)__ffsll((long long)after) : 64u - (uint32_t)lane;
         atomicAdd(reinterpret_cast<unsigned long long*>(g.table + key), (unsigned long long)run);
       }
-    }
+    });
   }
 }
 
@@ -3196,53 +3233,28 @@ __global__ __launch_bounds__(256) void k_hist(HistArgs g) {
 // stable LSD radix sort (so equal instants keep their (stream, line) order) and rendered into
 // one buffer.  Every step is reduce-then-scan over kernel boundaries; no block waits on another.
 
-// The parsed-and-since_ok bits of word w's 32 lines (parsed_word's loads).
-__device__ __forceinline__ uint32_t sel_word(const uint16_t* __restrict__ meta, uint64_t w, uint64_t L) {
-  const uint64_t l0 = w * 32;
-  uint32_t p = 0;
-  if (l0 + 32 <= L) {
-    const uint4* q = reinterpret_cast<const uint4*>(meta + l0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint4 v = q[k];
-      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t y = x[j] & (x[j] >> 1);  // bit 0 / bit 16: both flags of the low / high line
-        p |= ((y & 1u) | ((y >> 15) & 2u)) << (8 * k + 2 * j);
-      }
-    }
-  } else {
-    for (uint64_t l = l0; l < L; ++l) {
-      const uint32_t m = meta[l];
-      p |= (m & (m >> 1) & 1u) << (l - l0);
-    }
-  }
-  return p;
-}
-
 // Word w of E (0 past the line count): the selection word, the tail windows of the streams the
 // word meets, then the parsed / since_ok flags (read only where something is left).
 __device__ __forceinline__ uint32_t tl_e_word(const TlArgs& g, uint64_t w, uint64_t L) {
   const uint64_t l0 = w * 32;
   if (l0 >= L) return 0u;
   uint32_t x = word_range_mask(w, 0, L);
-  if (g.bits_in) x &= g.bits_in[w];
+  if (g.v.bits_in) x &= g.v.bits_in[w];
   if (!x) return 0u;
   const uint64_t l1 = l0 + 32 < L ? l0 + 32 : L;
   uint32_t win = 0;
-  for (uint32_t s = find_seg_by_line(g.a.segout, g.a.nsegs, l0); s < g.a.nsegs && g.a.segout[s].line_lo < l1; ++s)
-    win |= word_range_mask(w, g.a.segout[s].win_lo, g.a.segout[s].win_hi);
+  for (uint32_t s = find_seg_by_line(g.v.segout, g.v.nsegs, l0); s < g.v.nsegs && g.v.segout[s].line_lo < l1; ++s)
+    win |= word_range_mask(w, g.v.segout[s].win_lo, g.v.segout[s].win_hi);
   x &= win;
   if (!x) return 0u;
-  return x & sel_word(g.a.meta, w, L);
+  return x & meta_word<true>(g.v.meta, w, L);
 }
 
 __global__ __launch_bounds__(256) void k_tl_count(TlArgs g) {
   __shared__ uint32_t s_w[4];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.a.segout[g.a.nsegs - 1].line_hi;
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t;
     const uint32_t cnt = wave_sum((uint32_t)__popc(tl_e_word(g, w, L)));
     __syncthreads();  // (the previous chunk's sums are read)
@@ -3273,66 +3285,31 @@ __global__ __launch_bounds__(256) void k_tl_scan(uint64_t* __restrict__ a, uint6
   if (t == 255) a[m] = pre;  // (thread 255's range ends at m)
 }
 
-// The instant of the parsed line at segp + off (k_hist's two paths).
-__device__ __forceinline__ void tl_instant(const uint8_t* __restrict__ segp, uint64_t off, uint64_t seg_len,
-                                           int64_t& sec, int32_t& nsec) {
-  uint32_t p[6];
-  if (tw_canon_digits(segp, off, p)) {
-    canon_instant(p, sec, nsec);
-    return;
-  }
-  TsResult r;
-  uint32_t plen;
-  sec = 0;
-  nsec = 0;
-  if (parse_line_prefix(GlobalBytes{segp, (int64_t)off, (int64_t)seg_len}, r, plen)) {
-    sec = r.sec;
-    nsec = r.nsec;
-  }
-}
-
-// k_hist's walk over E: lane i of round r takes the wave's (64 r + i)-th line of E.  Its rank
-// in (stream, line) order is the chunk's base + the lines of the block's earlier waves + k.
+// The selected-line walk over E.  A line's rank in (stream, line) order is the chunk's base +
+// the lines of the block's earlier waves + its rank k in the wave.
 __global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
-  __shared__ uint32_t s_in[4][64], s_pre[4][64], s_seg[4][64], s_tot[4];
+  __shared__ WalkLds ws;
+  __shared__ uint32_t s_tot[4];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.a.segout[g.a.nsegs - 1].line_hi;
-  for (uint64_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    const uint32_t in = tl_e_word(g, w, L);
-    const uint32_t cnt = (uint32_t)__popc(in);
-    const uint32_t incl = wave_incl_scan_add(cnt, lane);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the wave's lines of E
-    __syncthreads();  // (the previous chunk's words are read)
-    s_in[wv][lane] = in;
-    s_pre[wv][lane] = incl - cnt;
-    s_seg[wv][lane] = in ? find_seg_by_line(g.a.segout, g.a.nsegs, l0) : 0u;
+    const uint32_t total = walk_publish(ws, g.v, tl_e_word(g, w, L), l0);
     if (lane == 0) s_tot[wv] = total;
     __syncthreads();
     uint64_t base = g.cbase[c];
     for (int k = 0; k < wv; ++k) base += s_tot[k];
-    const uint64_t wl0 = l0 - (uint64_t)lane * 32;  // first line of the wave's words
-    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
-      const uint32_t k = k0 + (uint32_t)lane;
-      if (k >= total) continue;
-      uint32_t j = 0;  // the word holding line k: the last one whose prefix is <= k (its count is > 0)
-#pragma unroll
-      for (uint32_t step = 32; step >= 1; step >>= 1)
-        if (s_pre[wv][j + step] <= k) j += step;
-      const uint32_t b = nth_set_bit(s_in[wv][j], k - s_pre[wv][j]);
-      const uint64_t l = wl0 + (uint64_t)j * 32 + b;  // (< L: `in` has no bit at or past L)
-      uint32_t s = s_seg[wv][j];
-      while (l >= g.a.segout[s].line_hi) ++s;  // (a word may span streams; s stays < nsegs as l < L)
-      const SegDesc sd = g.a.segs[s];
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
+      if (!q.live) return;
       int64_t sec;
       int32_t nsec;
-      tl_instant(g.a.bytes + sd.base, g.a.line_off[l + s], sd.len, sec, nsec);
-      const uint64_t ord = base + k;
+      if (!line_instant(g.v.bytes + q.sd.base, q.off, q.sd.len, sec, nsec)) sec = 0, nsec = 0;  // (none in E: parsed lines)
+      const uint64_t ord = base + q.k;
       if (ord < g.n) {  // (always: n is the scan's total of the same words)
         g.items[0][ord] = TlItem{(uint64_t)sec ^ (1ull << 63), (uint32_t)nsec, (uint32_t)ord};
-        g.side[ord] = TlSide{l, s, 0u};
+        g.side[ord] = TlSide{q.l, q.s, 0u};
       }
-    }
+    });
   }
 }
 
@@ -3468,17 +3445,17 @@ __device__ __forceinline__ TlGeom tl_geom(const TlArgs& g, const TlItem& it) {
   const TlSide sd = g.side[it.ord];
   const uint32_t s = sd.seg;
   const uint64_t l = sd.line;
-  if (s >= g.a.nsegs || l >= g.a.cap_lines) return q;
-  const SegDesc seg = g.a.segs[s];
-  const uint64_t ls = g.a.line_off[l + s], le = g.a.line_off[l + s + 1];
-  const uint32_t plen = g.timestamps ? 0u : line_plen(g.a, g.a.meta[l], g.a.bytes + seg.base, ls, le);
+  if (s >= g.v.nsegs || l >= g.v.cap_lines) return q;
+  const SegDesc seg = g.v.segs[s];
+  const uint64_t ls = g.v.line_off[l + s], le = g.v.line_off[l + s + 1];
+  const uint32_t plen = g.timestamps ? 0u : line_plen(g, g.v.meta[l], g.v.bytes + seg.base, ls, le);
   q.src = seg.base + ls + plen;
   q.len = (uint32_t)(le - ls - plen);
-  q.line = l - g.a.segout[s].line_lo;
+  q.line = l - g.v.segout[s].line_lo;
   q.seg = s;
   q.tag_off = g.tags ? g.segtab[3 * s + 1] : 0u;
   q.tag_len = g.tags ? g.segtab[3 * s + 2] : 0u;
-  q.nl = (le == seg.len && g.a.segout[s].frag) ? 1u : 0u;
+  q.nl = (le == seg.len && g.v.segout[s].frag) ? 1u : 0u;
   return q;
 }
 
@@ -3541,7 +3518,7 @@ __global__ __launch_bounds__(256) void k_tl_copy(TlArgs g, const TlItem* __restr
     const uint32_t n = (uint32_t)__shfl((int)q.len, (int)j, 64), to = (uint32_t)__shfl((int)q.tag_off, (int)j, 64),
                    tl = (uint32_t)__shfl((int)q.tag_len, (int)j, 64), nl = (uint32_t)__shfl((int)q.nl, (int)j, 64);
     for (uint32_t k = lane; k < tl; k += 64) g.out[o + k] = g.tags[to + k];
-    wave_copy(g.out + o + tl, g.a.bytes + src, n, lane);
+    wave_copy(g.out + o + tl, g.v.bytes + src, n, lane);
     if (nl && lane == 0) g.out[o + tl + n] = (uint8_t)'\n';
   }
 }
@@ -5356,6 +5333,13 @@ hipError_t launch_tcopy(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int nu
   return hipGetLastError();
 }
 
+// The grid of a kernel that takes one kMatchChunk chunk per block turn: 16 blocks per CU at
+// most, like k_mcount's (launch_tail_stage).
+static uint32_t chunk_grid(uint64_t nchunks, int num_cus) {
+  const uint64_t gmax = (uint64_t)num_cus * 16;
+  return (uint32_t)(nchunks < gmax ? nchunks : gmax);
+}
+
 hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int num_cus, uint32_t* ev_mask,
                          const RegroupArgs* g, const WindowArgs* tw) {
   uint32_t m_local = 0;
@@ -5364,8 +5348,7 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
   if (e != hipSuccess) return e;
   m |= 1u;
   if (g) {  // the selection bitmap first (a.bits = g->bits_out)
-    const uint64_t gmax = (uint64_t)num_cus * 16;
-    const uint32_t gc = (uint32_t)(g->nchunks < gmax ? g->nchunks : gmax);
+    const uint32_t gc = chunk_grid(g->v.nchunks, num_cus);
     hipLaunchKernelGGL(k_rg_sum, dim3(gc), dim3(256), 0, st, *g);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_rg_carry, dim3(1), dim3(256), 0, st, *g);
@@ -5373,9 +5356,8 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
     hipLaunchKernelGGL(k_rg_build, dim3(gc), dim3(256), 0, st, *g);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  if (tw && tw->nchunks) {  // then the time window (a.bits = tw->bits_out)
-    const uint64_t gmax = (uint64_t)num_cus * 16;
-    hipLaunchKernelGGL(k_tw_build, dim3((uint32_t)(tw->nchunks < gmax ? tw->nchunks : gmax)), dim3(256), 0, st, *tw);
+  if (tw && tw->v.nchunks) {  // then the time window (a.bits = tw->bits_out)
+    hipLaunchKernelGGL(k_tw_build, dim3(chunk_grid(tw->v.nchunks, num_cus)), dim3(256), 0, st, *tw);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_retail_init, dim3((a.nsegs + 255) / 256 < 1024 ? (a.nsegs + 255) / 256 : 1024), dim3(256), 0,
@@ -5389,31 +5371,28 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
 hipError_t launch_hist(const HistArgs& g, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int num_cus) {
   hipError_t e = hipEventRecord(ev0, st);
   if (e != hipSuccess) return e;
-  if ((e = hipMemsetAsync(g.table, 0, (size_t)g.nsegs * (g.n_buckets + 2) * 8, st)) != hipSuccess) return e;
-  if (g.nchunks) {
-    const uint64_t gmax = (uint64_t)num_cus * 16;
-    hipLaunchKernelGGL(k_hist, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+  if ((e = hipMemsetAsync(g.table, 0, (size_t)g.v.nsegs * (g.n_buckets + 2) * 8, st)) != hipSuccess) return e;
+  if (g.v.nchunks) {
+    hipLaunchKernelGGL(k_hist, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipEventRecord(ev1, st);
 }
 
 hipError_t launch_tl_count(const TlArgs& g, hipStream_t st, int num_cus) {
-  if (g.nchunks) {
-    const uint64_t gmax = (uint64_t)num_cus * 16;
-    hipLaunchKernelGGL(k_tl_count, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+  if (g.v.nchunks) {
+    hipLaunchKernelGGL(k_tl_count, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.nchunks);
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.v.nchunks);
   return hipGetLastError();
 }
 
 hipError_t launch_tl_keys(const TlArgs& g, hipStream_t st, int num_cus) {
   hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
   if (e != hipSuccess) return e;
-  if (!g.n || !g.nchunks) return hipSuccess;
-  const uint64_t gmax = (uint64_t)num_cus * 16;
-  hipLaunchKernelGGL(k_tl_keys, dim3((uint32_t)(g.nchunks < gmax ? g.nchunks : gmax)), dim3(256), 0, st, g);
+  if (!g.n || !g.v.nchunks) return hipSuccess;
+  hipLaunchKernelGGL(k_tl_keys, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const uint64_t nb = (g.n + 255) / 256, dmax = (uint64_t)num_cus * 8;
   hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items[0], g.n, g.dhist);

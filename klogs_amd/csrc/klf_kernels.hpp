@@ -361,41 +361,42 @@ struct RunArgs {
   uint64_t* fuse_rinfo;
 };
 
-// Context lines / inverted match over a finished run (klf_regroup, SPEC.md S4a): the
-// regroup kernels read the run's match bitmap M and its line meta and write the selection
-// bitmap G' the tail stage then runs over.  Their own arguments: RunArgs, and with it every
-// kernel of the run itself, stays as it is.
-struct RegroupArgs {
-  const uint32_t* bits_in;  // M, [cap_lines / 32 + 1]
-  uint32_t* bits_out;       // G', same layout
+// What the kernels over a finished run's selected lines read of it (the regroup, time-window,
+// histogram and timeline kernels; the host fills it in one place, sel_view in klf_engine.cpp).
+struct SelView {
+  const uint32_t* bits_in;  // the selection bitmap the kernel reads (M, G' or G''), [cap_lines / 32 + 1];
+                            // null: the parsed lines (no patterns)
   const uint16_t* meta;     // [cap_lines]
+  const uint64_t* line_off; // [cap_lines + nsegs] the run's line index
+  const uint8_t* bytes;     // the batch
+  const SegDesc* segs;      // [nsegs]
   const SegOut* segout;     // [nsegs] (line_lo / line_hi; the line count is the last line_hi)
   uint32_t nsegs;
-  uint32_t invert;          // S = parsed lines not in M
   uint64_t cap_lines;
+  uint64_t nchunks;         // kMatchChunk chunks holding lines
+};
+
+// Context lines / inverted match over a finished run (klf_regroup, SPEC.md S4a): the
+// regroup kernels read the run's match bitmap M (v.bits_in) and its line meta and write the
+// selection bitmap G' the tail stage then runs over.  Their own arguments: RunArgs, and with
+// it every kernel of the run itself, stays as it is.
+struct RegroupArgs {
+  SelView v;                // (meta, segout, nsegs, cap_lines, nchunks; bits_in = M, never null)
+  uint32_t* bits_out;       // G', same layout as M
+  uint32_t invert;          // S = parsed lines not in M
   uint64_t before, after;   // context lines before / after a line of S
   // per kMatchChunk chunk c: [0] last line of S in the chunk + 1 (0 = none), [1] ~(its first
   // line) (0 = none); then the same over the chunks before c ([2]) / after c ([3]);
-  // 4 * nchunks u64, nchunks = cap_lines / kMatchChunk + 1
+  // 4 * (cap_lines / kMatchChunk + 1) u64
   uint64_t* csum;
-  uint64_t nchunks;
 };
 
 // Time window over a finished run (klf_window, SPEC.md S4b): k_tw_build reads a selection
 // bitmap G' and, for each of its lines, the first 32 bytes of the line in the resident batch,
 // and writes G'' = the lines of G' whose instant lies in [from, until).
 struct WindowArgs {
-  const uint32_t* bits_in;  // G', [cap_lines / 32 + 1]; null: the parsed lines (no patterns).
-                            // May be bits_out (a thread reads its word before it writes it)
+  SelView v;                // bits_in = G'; may be bits_out (a thread reads its word before it writes it)
   uint32_t* bits_out;       // G'', same layout
-  const uint16_t* meta;     // [cap_lines]
-  const uint64_t* line_off; // [cap_lines + nsegs] the run's line index
-  const uint8_t* bytes;     // the batch
-  const SegDesc* segs;      // [nsegs]
-  const SegOut* segout;     // [nsegs]
-  uint32_t nsegs;
-  uint64_t cap_lines;
-  uint64_t nchunks;         // kMatchChunk chunks holding lines
   int64_t from_sec, until_sec;
   int32_t from_nsec, until_nsec;
   uint32_t from_dig[6], until_dig[6];  // the bounds packed like RunArgs::since_dig
@@ -406,16 +407,8 @@ struct WindowArgs {
 // `org`, in bucket floor((ts - org) / width_ns), or at / above `end` = org + n_buckets * width_ns.
 // It writes the table alone: the run's arrays are only read.
 struct HistArgs {
-  const uint32_t* bits_in;  // M, G' or G'', [cap_lines / 32 + 1]; null: the parsed lines (no patterns)
-  const uint16_t* meta;     // [cap_lines]
-  const uint64_t* line_off; // [cap_lines + nsegs] the run's line index
-  const uint8_t* bytes;     // the batch
-  const SegDesc* segs;      // [nsegs]
-  const SegOut* segout;     // [nsegs]
-  uint32_t nsegs;
+  SelView v;
   uint32_t n_buckets;
-  uint64_t cap_lines;
-  uint64_t nchunks;         // kMatchChunk chunks holding lines
   int64_t org_sec, end_sec;
   int32_t org_nsec, end_nsec;
   uint32_t end_open;        // org + the span leaves int64 seconds: no line is above
@@ -427,7 +420,7 @@ struct HistArgs {
 // Merged timeline of a finished run (klf_result_timeline, SPEC.md S4d): the emitted lines E of
 // all streams, sorted by (sec, nsec, stream, line) and rendered into one buffer.
 //   k_tl_count / k_tl_scan    E lines per kMatchChunk chunk, their exclusive prefix -> n
-//   k_tl_keys                 k_hist's walk over E: item[ord] = the line's instant, side[ord] =
+//   k_tl_keys                 the selected-line walk over E: item[ord] = the line's instant, side[ord] =
 //                             its (line, segment); ord = its rank in (stream, line) order
 //   k_tl_digits               the twelve 256-bin histograms of the 96-bit key in one read
 //   k_tl_bcount / k_tl_bscan / k_tl_scatter   one stable LSD pass (8-bit digit) between the two
@@ -455,9 +448,7 @@ constexpr uint32_t kTlDigits = 12;          // 8-bit digits of the key: nsec byt
 constexpr uint32_t kTlSortBlock = 2048;     // items per block of a radix pass (8 rounds of 256)
 constexpr uint32_t kTlPlanBlock = 256;      // sorted positions per block of the plan / copy
 struct TlArgs {
-  RunArgs a;                // the run (read only): meta, line_off, bytes, segs, segout, nsegs
-  const uint32_t* bits_in;  // the selection bitmap (M, G' or G''); null: every line (no patterns)
-  uint64_t nchunks;         // kMatchChunk chunks holding lines
+  SelView v;                // bits_in null: every line (no patterns)
   uint32_t timestamps;      // render the line's prefix too
   const uint32_t* segtab;   // [3 * nsegs] per segment: stream id, tag offset, tag length
   const uint8_t* tags;      // the tag bytes (null: no tags, every length 0)
@@ -497,7 +488,7 @@ hipError_t launch_scatter(const RunArgs& a, hipStream_t stream, int num_cus);
 hipError_t launch_pipeline(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus, int phase = 0,
                            uint32_t* ev_mask = nullptr);
 // Re-runs matched counts, tail and compaction of the last pipeline with a.tail changed.
-// g (nullable): first builds the selection bitmap g->bits_out (= a.bits) from g->bits_in
+// g (nullable): first builds the selection bitmap g->bits_out (= a.bits) from g->v.bits_in
 // (k_rg_sum / k_rg_carry / k_rg_build), inside the same ev[0] .. ev[5] bracket.
 // tw (nullable): then cuts it by a time window (k_tw_build; tw->bits_out = a.bits), same bracket.
 hipError_t launch_retail(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus,
