@@ -991,6 +991,26 @@ static hipError_t wait_stream(hipStream_t st, uint64_t spin_us) {
   }
 }
 
+// An attempt's counters (the first 32) and stream records, and `ext` bytes of a one-pass run's extents
+// behind them in h_rb, to the host: the copies on the engine stream, then the wait (`spin_us` of polling,
+// 0: a blocking sync).  `*where`, if given, names the sync on entry and the call that failed on return.
+static hipError_t read_back(klf_engine* e, uint32_t nsegs, size_t ext, uint64_t spin_us, uint32_t* counters, SegOut* so,
+                            const char** where = nullptr) {
+  uint8_t* rb = e->h_rb.as<uint8_t>();
+  const size_t n = kCtrBytes + nsegs * sizeof(SegOut);
+  const char* sync = where ? *where : "";
+  if (where) *where = "D2H counters + records";
+  hipError_t h = hipMemcpyAsync(rb, e->d_counters.p, n, hipMemcpyDeviceToHost, e->stream);
+  if (h != hipSuccess) return h;
+  if (where && ext) *where = "D2H extents";
+  if (ext && (h = hipMemcpyAsync(rb + n, e->d_fext.p, ext, hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return h;
+  if (where) *where = sync;
+  if ((h = spin_us ? wait_stream(e->stream, spin_us) : hipStreamSynchronize(e->stream)) != hipSuccess) return h;
+  memcpy(counters, rb, 32 * sizeof(uint32_t));
+  memcpy(so, rb + kCtrBytes, nsegs * sizeof(SegOut));
+  return hipSuccess;
+}
+
 // Output bigger than the buffer (counters[kCtrOutShort], from k_cmove / k_tcopy, which
 // skipped the copies that would not fit but still wrote every stream's output range): grow
 // the buffer to the run's output and rerun the tail stage over the line index and bitmap
@@ -1007,13 +1027,9 @@ static hipError_t grow_out_retail(klf_engine* e, klf::RunArgs& a, std::vector<Se
     a.out = e->d_out.as<uint8_t>();
     a.out_cap = e->d_out.cap;
     if ((h = klf::launch_retail(a, e->stream, e->ev, e->num_cus)) != hipSuccess) return h;
-    uint32_t* rb = static_cast<uint32_t*>(e->h_rb.p);  // counters, then the stream records
-    if ((h = hipMemcpyAsync(rb, e->d_counters.p, kCtrBytes + so.size() * sizeof(SegOut), hipMemcpyDeviceToHost,
-                            e->stream)) != hipSuccess)
-      return h;
-    if ((h = hipStreamSynchronize(e->stream)) != hipSuccess) return h;
-    memcpy(so.data(), reinterpret_cast<uint8_t*>(rb) + kCtrBytes, so.size() * sizeof(SegOut));
-    if (!rb[klf::kCtrOutShort]) return hipSuccess;
+    uint32_t counters[32];
+    if ((h = read_back(e, (uint32_t)so.size(), 0, 0, counters, so.data())) != hipSuccess) return h;
+    if (!counters[klf::kCtrOutShort]) return hipSuccess;
   }
   return hipErrorOutOfMemory;  // the ranges did not settle (cannot happen: they do not depend on the buffer)
 }
@@ -1022,7 +1038,7 @@ static hipError_t grow_out_retail(klf_engine* e, klf::RunArgs& a, std::vector<Se
 // event nodes are not re-recorded by a replay) as a replayed graph, bracketed by ev[0] /
 // ev[5] on the engine stream.  Returns false when the run should launch eagerly instead:
 // a first sighting of these arguments, or a capture that failed (then never again).
-static bool launch_graph(klf_engine* e, const klf::RunArgs& a, uint32_t& ev_mask) {
+static bool launch_graph(klf_engine* e, const klf::RunArgs& a, uint32_t& ev_mask, bool diag) {
   const uint8_t* k = reinterpret_cast<const uint8_t*>(&a);
   std::vector<uint8_t> key(k, k + sizeof(a));
   key.insert(key.end(), reinterpret_cast<const uint8_t*>(&e->num_cus),
@@ -1055,7 +1071,7 @@ static bool launch_graph(klf_engine* e, const klf::RunArgs& a, uint32_t& ev_mask
       if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
       e->gexec = nullptr;
       e->graph_off = true;
-      if (getenv("KLF_DIAG")) fprintf(stderr, "[klf] graph capture failed: eager launches from here on\n");
+      if (diag) fprintf(stderr, "[klf] graph capture failed: eager launches from here on\n");
       return false;
     }
     e->gkey = std::move(key);
@@ -1071,6 +1087,604 @@ static bool launch_graph(klf_engine* e, const klf::RunArgs& a, uint32_t& ev_mask
   return true;
 }
 
+// ---- The run on the host: the knobs, the plan, what a redo changes, the steps ----
+using Clock = std::chrono::steady_clock;
+using BufList = std::vector<std::pair<DevBuf*, size_t>>;
+// Every KLF_* variable of the run path (DESIGN.md 4a lists what each does), read once per run:
+// tests flip them between the runs of one process.
+struct RunKnobs {
+  bool diag, two_phase, one_phase, tindex_wide, graph;
+  bool qf_tune, fuse, lazy_index, plan_runs, win_index, win_index_rx, skip_idle;  // KLF_<NAME>=0 turns each off
+  uint64_t graph_max, cap_clamp, out_init, pool_cap;
+  uint32_t scatter_split;
+  const char *fuse_range, *nl_scale, *compact, *wave_pool, *plan_mode, *timeline_out;  // parsed where they apply
+};
+static bool knob_off(const char* name) { const char* v = getenv(name); return v && !strcmp(v, "0"); }
+static RunKnobs read_knobs() {
+  auto num = [](const char* name, long lo, int64_t unset) {  // a number, at least `lo`
+    const char* v = getenv(name);
+    return (uint64_t)(v ? (int64_t)std::max(lo, atol(v)) : unset);
+  };
+  RunKnobs k;
+  k.diag = getenv("KLF_DIAG"); k.two_phase = getenv("KLF_TWO_PHASE"); k.one_phase = getenv("KLF_ONE_PHASE");
+  k.tindex_wide = getenv("KLF_DEBUG_TINDEX_WIDE");
+  k.graph = getenv("KLF_GRAPH") && !knob_off("KLF_GRAPH");  // (opt-in)
+  k.graph_max = num("KLF_GRAPH_MAX_MB", 0, 256) << 20;
+  k.qf_tune = !knob_off("KLF_QF_TUNE"); k.fuse = !knob_off("KLF_FUSE"); k.lazy_index = !knob_off("KLF_LAZY_INDEX");
+  k.plan_runs = !knob_off("KLF_PLAN_RUNS"); k.skip_idle = !knob_off("KLF_SKIP_IDLE");
+  k.win_index = !knob_off("KLF_WIN_INDEX"); k.win_index_rx = !knob_off("KLF_WIN_INDEX_RX");
+  k.cap_clamp = num("KLF_DEBUG_CAP_CLAMP", 1, -1); k.out_init = num("KLF_DEBUG_OUT_INIT", 1, 64ll << 20);  // (~0: none)
+  k.pool_cap = num("KLF_DEBUG_POOL_CAP", 1, 0); k.scatter_split = (uint32_t)num("KLF_SCATTER_SPLIT", 0, 0);
+  k.fuse_range = getenv("KLF_DEBUG_FUSE_RANGE"); k.nl_scale = getenv("KLF_DEBUG_NL_SCALE");
+  k.compact = getenv("KLF_COMPACT"); k.wave_pool = getenv("KLF_WAVE_POOL"); k.plan_mode = getenv("KLF_PLAN_MODE");
+  k.timeline_out = getenv("KLF_TIMELINE_OUT");
+  return k;
+}
+struct RunPlan {  // what stays fixed through a run's attempts
+  klf_engine* e; const klf_filter* f; const uint8_t* d_bytes; RunKnobs k;  // (aggregate-initialised: keep first)
+  std::vector<SegDesc> segs;  // the non-empty streams
+  uint32_t nsegs = 0, compact_mode = 0, qhits_cap = 0;
+  uint64_t ntiles = 0, total_bytes = 0, hflat_cap = 0, out_need = 0, seg_end = 0;  // seg_end: past the last input byte
+  klf::CompiledSet::Mode mode = klf::CompiledSet::kNone;
+  bool count = false;        // per-pattern counts are evaluated
+  bool same_layout = false;  // the last run's streams: d_segs / d_tile_seg stand
+  bool small_first = false;  // a first batch that maps its 32-B-rule line arrays as they are
+  bool want_truns = false, fuse_try = false, lazy_index = false, full_index = false, need_cand = false,
+       need_hits = false;
+  hipEvent_t* evs = nullptr;  // KLF_FILTER_NO_TIMING: none (launch_pipeline records none)
+  bool gram = false;          // the first batch's sample (start_sample): the gram histogram is in flight,
+  uint32_t nl_blocks = 0;     // or the newline count over this many tiles (0: neither)
+  bool density_cap = false, wave_pool = false;  // (what the sample's density decides: plan_density)
+  Clock::time_point t_run0 = Clock::now(), t_tune0;  // KLF_DIAG: wall-clock marks through the run
+  uint64_t alloc0 = g_alloc_ns.load(), tune_ns = 0;
+  std::vector<std::pair<const char*, Clock::time_point>> marks;
+  void mark(const char* what) { if (k.diag) marks.emplace_back(what, Clock::now()); }
+};
+struct RunState {  // what a redo changes (apply_outcome), besides e->pool_cap and e->pairs_log2
+  uint64_t cap = 0;           // line capacity of the next attempt
+  uint32_t pool_chunk = 256;  // the wave pool's chunk size (pool_need)
+  bool fuse_ok = false, win_ok = false;  // one-pass compaction; windowed line index
+  bool force_match = false;              // an overflowed hit list / NFA queue: k_match decides
+  int line_reruns = 0, pair_reruns = 0;
+};
+// What an attempt asks for.  kLines: more lines (or pool slots) than estimated; kMatch: an overflowed hit list or
+// queue with k_match skipped; kFuse: the one pass was voided; kIndex: the whole line index is needed; kPairs: set full.
+enum Outcome { kDone, kLines, kMatch, kFuse, kIndex, kPairs };
+static const char* const kOutcomeName[] = {"done", "lines", "match", "fuse", "index", "pairs"};
+enum Next { kStand, kRedo, kFail };  // what follows an attempt: its result stands, another attempt, the run fails
+struct Attempt {
+  klf::RunArgs a;
+  uint32_t counters[32];
+  uint32_t ev_mask;   // the events this attempt recorded (the timing queries read only those)
+  const char* shape;  // plain / graph / two-phase / ac-split
+  bool phase1;        // ended at phase 1's readback (kLines)
+  bool tcopy, grown;  // in-place relaunches (the deferred k_tcopy, grow_out_retail); they clear the fields
+  uint32_t skip_tcopy, plan_mode, plan_runs;  // kept here as launched, for the KLF_DIAG line
+};
+static void learn_density(klf_engine* e, const std::vector<SegOut>& so, uint64_t total_bytes) {
+  e->line_density = (double)(so.back().line_hi + 1) / (double)total_bytes;
+}
+static void bump_pool(klf_engine* e, const uint32_t* counters) {  // what the scan reserved + every wave's last chunk
+  e->pool_cap = std::max<uint64_t>(e->pool_cap, (uint64_t)counters[klf::kCtrPool] + (uint64_t)e->num_cus * 16 * 4096);
+}
+static uint64_t learned_cap(const RunPlan& p) {  // line capacity from the last run's line density (+25 %)
+  return (uint64_t)(p.e->line_density * (double)p.total_bytes * 1.25) + 2ull * p.nsegs + 4096;
+}
+static uint32_t seg_of_tile(const std::vector<SegDesc>& segs, uint64_t t) {
+  uint32_t lo = 0, hi = (uint32_t)segs.size();  // the last segment whose tile0 <= t
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (segs[mid].tile0 <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// The first run asking for per-pattern counts of a set with an always-pattern compiles the other
+// patterns (klf_open kept the set as kAll); if that fails the counts are reported unavailable.
+static int compile_pending(klf_engine* e) {
+  if (const int rc = ensure_ac(e); rc != KLF_OK) return rc;
+  klf::CompiledSet full;
+  std::string cerr; int ccode = KLF_OK;
+  if (klf::compile_set(e->pend_pats, e->pend_kinds, full, cerr, ccode, !e->tune_later, false)) {
+    e->cs = std::move(full);
+    e->dpats.n_cids = e->cs.n_cids; e->dpats.n_lits = e->cs.n_lits;
+    HIPCHK(e, upload_pattern_tables(e, e->tune_later), "upload pattern tables");
+  } else {
+    e->cs.also_all_pending = false;
+    e->counts_code = ccode; e->counts_err = "per-pattern counts unavailable: " + cerr;
+  }
+  return KLF_OK;
+}
+static int layout_segments(RunPlan& p, RunState& s, klf_result* r, uint32_t n_streams, const uint64_t* seg_base,
+                           const uint64_t* lens) {
+  for (uint32_t i = 0; i < n_streams; ++i) {
+    if (!lens[i]) continue;
+    if (seg_base[i] % klf::kSegAlign) return set_err(p.e, KLF_EINVAL, "seg_base must be 256-B aligned");
+    SegDesc d;
+    d.base = seg_base[i]; d.len = lens[i]; d.tile0 = (uint32_t)p.ntiles;
+    d.ntiles = (uint32_t)((lens[i] + klf::kTile - 1) / klf::kTile);
+    r->seg_of[i] = (int64_t)p.segs.size();
+    p.segs.push_back(d); r->seg_base.push_back(d.base);
+    p.ntiles += d.ntiles; p.total_bytes += lens[i];
+    s.cap += lens[i] / 32 + 2;  // kubelet lines carry a >= 31-byte prefix; overflow -> exact rerun
+  }
+  if (p.ntiles >= (1ull << 32)) return set_err(p.e, KLF_EINVAL, "batch too large");
+  p.nsegs = (uint32_t)p.segs.size();
+  if (p.e->line_density > 0.0) s.cap = std::min<uint64_t>(s.cap, learned_cap(p));
+  return KLF_OK;
+}
+
+static void plan_run(RunPlan& p, RunState& s) {
+  klf_engine* e = p.e;
+  const klf_filter* f = p.f;
+  const bool general = p.mode == klf::CompiledSet::kGeneral, none = p.mode == klf::CompiledSet::kNone;
+  s.cap = std::min(s.cap, p.k.cap_clamp);
+  p.same_layout = p.segs.size() == e->last_segs.size() && e->d_tile_seg.cap >= p.ntiles * 4 &&
+                  memcmp(p.segs.data(), e->last_segs.data(), p.segs.size() * sizeof(SegDesc)) == 0;
+  // (32-B-rule line arrays of at most ~2 GB are mapped as they are: no sample, no sync before the scan)
+  p.small_first = e->line_density == 0.0 && s.cap * 11 <= (2ull << 30) && !p.k.two_phase && !p.k.nl_scale;
+  // the dense compaction's per-tile run table only without --tail or once a --tail run went dense (else k_tcopy lists)
+  p.want_truns = f->tail < 0 || e->dense_tail_seen;
+  if (const char* v = p.k.compact) p.compact_mode = !strcmp(v, "sparse") ? 1u : !strcmp(v, "dense") ? 2u : 0u;
+  // a --tail run selects at most S (N + 1) lines: up to 2^20 the line gather is the path (no tile-copy tables)
+  else if (f->tail >= 0 && (uint64_t)p.nsegs * ((uint64_t)f->tail + 1) <= (1ull << 20)) p.compact_mode = 1;
+  // one-pass compaction (no patterns, --tail -1): the fused scan compacts each wave's tile range in place
+  s.fuse_ok = p.fuse_try = none && f->tail < 0 && p.compact_mode == 0 && p.k.fuse;
+  for (const auto& d : p.segs) p.seg_end = std::max<uint64_t>(p.seg_end, d.base + d.len);
+  p.evs = (f->flags & KLF_FILTER_NO_TIMING) ? nullptr : e->ev;
+  p.full_index = (f->flags & KLF_FILTER_FULL_INDEX) != 0; s.win_ok = !p.full_index;
+  p.lazy_index = none && f->tail < 0 && !p.full_index && p.k.lazy_index;  // lazy line index (grep none, --tail -1)
+  // the output buffer: the input's size without --tail, else grown on demand (a --tail run never maps as much)
+  if (f->tail < 0) p.out_need = std::max<uint64_t>(p.total_bytes, p.fuse_try ? p.seg_end : 0) + 64;
+  else if (!e->d_out.p)  // a first --tail run: room for a typical tail window (no rerun to grow)
+    p.out_need = std::min<uint64_t>(p.total_bytes + 64, p.k.out_init);
+  p.need_hits = general && e->cs.qf_on; p.need_cand = p.need_hits && e->cs.rx_count;
+  // bitmap hits: kHitSlots per tile in place; spills beyond 1 per 8 KiB of input -> k_match decides
+  p.qhits_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(p.total_bytes / 8192, 1u << 16), e->hits_cap_max);
+  // flattened hit slots: up to 1 per 4 KiB of input (2 per tile); more -> k_match decides
+  p.hflat_cap = std::min<uint64_t>(std::max<uint64_t>(p.total_bytes / 4096, 1u << 20),
+                                   (uint64_t)p.ntiles * klf::kHitSlots);
+  p.count = (f->flags & KLF_FILTER_PATTERN_COUNTS) && general && e->cs.n_cids;
+}
+static int upload_layout(RunPlan& p) {  // unless the last run's segment table and tile map stand
+  klf_engine* e = p.e;
+  p.mark("pre-segs");
+  if (!p.same_layout) {
+    HIPCHK(e, e->d_segs.ensure(p.nsegs * sizeof(SegDesc)), "alloc segs");
+    p.mark("segs alloc");
+    // (a pageable source: staged before the call returns, so no stream sync is needed)
+    HIPCHK(e, hipMemcpyAsync(e->d_segs.p, p.segs.data(), p.nsegs * sizeof(SegDesc), hipMemcpyHostToDevice, e->stream),
+           "H2D segs");
+    p.mark("segs copy");
+    HIPCHK(e, e->d_tile_seg.ensure(p.ntiles * 4 + 16), "alloc tile_seg");  // + whole 16-B loads past the end
+  }
+  p.mark("segs");
+  return KLF_OK;
+}
+
+// The first batch's sample, read back while the host maps the workspace: a prefiltered set's gram statistics
+// (they place the needles' sampling windows, their newline share sizes the line arrays), else, but for a small
+// batch, a newline count over 64 tiles -- no readback between the scan and the rest of the pipeline.
+static int start_sample(RunPlan& p) {
+  klf_engine* e = p.e;
+  hipStream_t st = e->stream;
+  if (p.mode == klf::CompiledSet::kGeneral && e->cs.qf_on && !e->cs.qf_tuned) {
+    e->cs.qf_tuned = true; p.t_tune0 = Clock::now(); p.gram = p.k.qf_tune;
+  }
+  if (!p.gram && (e->line_density != 0.0 || p.small_first || p.k.two_phase)) return KLF_OK;
+  if (!p.gram) p.nl_blocks = (uint32_t)std::min<uint64_t>(p.ntiles, 64);
+  const size_t nb = p.gram ? klf::kGramHistWords * 4 : (size_t)p.nl_blocks * 8;
+  HIPCHK(e, e->d_hist.ensure(nb), p.gram ? "alloc hist" : "alloc line sample");
+  HIPCHK(e, e->h_hist.ensure(nb), p.gram ? "alloc hist readback" : "alloc line sample readback");
+  if (p.gram)
+    HIPCHK(e, klf::launch_gramhist(p.d_bytes, e->d_segs.as<SegDesc>(), p.nsegs, klf::kGramHistSample, e->cs.qf_fold,
+                                   e->d_hist.as<uint32_t>(), st), "gram histogram");
+  else
+    HIPCHK(e, klf::launch_nlsample(p.d_bytes, e->d_segs.as<SegDesc>(), p.nsegs, (uint32_t)p.ntiles, p.nl_blocks,
+                                   e->d_hist.as<uint32_t>(), st), "line sample");
+  HIPCHK(e, hipMemcpyAsync(e->h_hist.p, e->d_hist.p, nb, hipMemcpyDeviceToHost, st), p.gram ? "D2H hist" : "D2H line sample");
+  return KLF_OK;
+}
+// Waits for the sample; `est`: its lines per byte.  The gram form also lays out and uploads the prefilter.
+static int finish_sample(RunPlan& p, double& est) {
+  klf_engine* e = p.e;
+  if (!p.gram && !p.nl_blocks) return KLF_OK;
+  HIPCHK(e, hipStreamSynchronize(e->stream), p.gram ? "sync hist" : "sync line sample");
+  const uint32_t* hv = e->h_hist.as<uint32_t>();
+  if (!p.gram) {
+    uint64_t nl = 0, nb = 0;
+    for (uint32_t b = 0; b < p.nl_blocks; ++b) { nl += hv[2 * b]; nb += hv[2 * b + 1]; }
+    if (nb) est = (double)(nl + p.nl_blocks) / (double)nb;  // (+1 per tile: a margin, never 0)
+    if (p.k.nl_scale) est *= atof(p.k.nl_scale);
+    p.mark("line sample");
+    return KLF_OK;
+  }
+  const auto t_hist = Clock::now();
+  klf::DataStats ds;
+  ds.bytes.assign(256, 0);
+  for (int c = 0; c < 256; ++c) { ds.bytes[c] = hv[c]; ds.nbytes += hv[c]; }
+  ds.pair.assign(hv + klf::kGramHistPairs, hv + klf::kGramHistPairs + 65536);
+  for (auto& c : ds.pair) c *= 2;  // counted at every 2nd position
+  klf::stats_finish(ds);
+  if (ds.nbytes) est = (double)(ds.bytes['\n'] + 1) / (double)ds.nbytes;
+  klf::place_needles(e->cs, &ds);
+  const auto t_place = Clock::now();
+  if (p.k.diag)
+    fprintf(stderr, "[klf] prefilter layout from %llu sampled bytes: %s\n", (unsigned long long)ds.nbytes,
+            e->cs.qf_layout.c_str());
+  HIPCHK(e, upload_prefilter(e), "upload prefilter tables");
+  if (p.k.diag)
+    fprintf(stderr, "[klf] first-batch tuning: statistics %.1f us (with the workspace mapped meanwhile), layout %.1f us, uploads %.1f us\n",
+            std::chrono::duration<double, std::micro>(t_hist - p.t_tune0).count(),
+            std::chrono::duration<double, std::micro>(t_place - t_hist).count(),
+            std::chrono::duration<double, std::micro>(Clock::now() - t_place).count());
+  p.tune_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - p.t_tune0).count();
+  p.mark("first-batch tuning");
+  return KLF_OK;
+}
+// what the sample's line density decides: a first run's line capacity (x2 + a margin) and the slot storage
+static void plan_density(RunPlan& p, RunState& s, double est) {
+  klf_engine* e = p.e;
+  p.density_cap = e->line_density == 0.0 && est > 0.0 && !p.k.two_phase;
+  // slots of tiles with two or more line starts: lines over 1 KiB -> per-wave pool chunks, else per-tile records
+  const double dens = e->line_density > 0.0 ? e->line_density : est;
+  p.wave_pool = p.k.wave_pool ? strcmp(p.k.wave_pool, "0") != 0 : (dens > 0.0 && dens * 1024.0 < 1.0);
+  if (p.density_cap) s.cap = std::min<uint64_t>(s.cap, (uint64_t)(est * (double)p.total_bytes * 2.0) + 2ull * p.nsegs + 65536);
+}
+// the one-pass ranges (n x kScanGroup tiles, one per wave of a full launch) and each one's first extent
+static int fuse_ranges(RunPlan& p) {
+  klf_engine* e = p.e;
+  const uint64_t waves = (uint64_t)std::max(1, klf::fuse_waves(e->num_cus));
+  uint64_t R = (p.ntiles + waves - 1) / waves;
+  R = (R + klf::kScanGroup - 1) / klf::kScanGroup * klf::kScanGroup;
+  if (p.k.fuse_range) R = std::max<uint64_t>(klf::kScanGroup, (uint64_t)atol(p.k.fuse_range) / klf::kScanGroup * klf::kScanGroup);
+  const uint32_t nr = (uint32_t)((p.ntiles + R - 1) / R);
+  const bool same_fuse_layout = p.segs.size() == e->fuse_segs.size() &&
+                                memcmp(p.segs.data(), e->fuse_segs.data(), p.segs.size() * sizeof(SegDesc)) == 0;
+  if (!same_fuse_layout || e->fuse_range != (uint32_t)R || e->fuse_nranges != nr) {
+    e->fuse_segs.clear(); e->fuse_ext0.assign(nr + 1, 0);  // (fuse_segs: invalid until the table is on its way)
+    for (uint32_t q = 0; q < nr; ++q) {
+      const uint64_t t0 = (uint64_t)q * R, t1 = std::min<uint64_t>(t0 + R, p.ntiles) - 1;
+      e->fuse_ext0[q + 1] = e->fuse_ext0[q] + (seg_of_tile(p.segs, t1) - seg_of_tile(p.segs, t0) + 1);
+    }
+    HIPCHK(e, e->d_fext0.ensure((nr + 1) * 4), "alloc fuse ranges");
+    HIPCHK(e, hipMemcpyAsync(e->d_fext0.p, e->fuse_ext0.data(), (nr + 1) * 4, hipMemcpyHostToDevice, e->stream),
+           "H2D fuse ranges");
+    e->fuse_range = (uint32_t)R; e->fuse_nranges = nr; e->fuse_next = e->fuse_ext0[nr];
+    e->fuse_segs = p.segs;
+  }
+  HIPCHK(e, e->d_fext.ensure((size_t)e->fuse_next * 16), "alloc fuse extents");
+  HIPCHK(e, e->d_frinfo.ensure((size_t)e->fuse_nranges * 32), "alloc fuse range states");
+  return KLF_OK;
+}
+static int map_workspace(RunPlan& p) {  // what the layout alone sizes, as one allocation
+  klf_engine* e = p.e;
+  const uint64_t ntiles = p.ntiles;
+  BufList ws = {{&e->d_tstat, ntiles * sizeof(klf::TileStat)},
+                {&e->d_tile_base, ntiles * 8}, {&e->d_bsum, (ntiles / 1024 + 2) * 4 * 8},
+                {&e->d_counters, kCtrBytes + p.nsegs * sizeof(SegOut)} /* + the stream records */,
+                {&e->d_wpre, (3 * (size_t)p.nsegs + 2) * 8} /* + wgrp */};
+  if (p.want_truns) ws.push_back({&e->d_truns, ntiles * klf::kRunSlots * 4});
+  if (p.compact_mode != 1) ws.insert(ws.end(), {{&e->d_trec, ntiles * sizeof(klf::TRec)}, {&e->d_kbase, ntiles * 16}});
+  if (p.need_cand) ws.push_back({&e->d_cand, (size_t)e->cand_cap * 16});
+  if (p.need_hits)
+    ws.insert(ws.end(), {{&e->d_qhits, (size_t)p.qhits_cap * 8}, {&e->d_hslots, (size_t)ntiles * klf::kHitSlots * 2},
+                         {&e->d_hflat, (size_t)p.hflat_cap * 8}});
+  HIPCHK(e, ensure_all(e->d_block, e->block_users, ws), "alloc workspace");
+  p.mark("workspace");
+  return KLF_OK;
+}
+// the buffers indexed by global line, and the compaction's `mcb` blocks and `cmc` copy chunks, for capacity c
+static BufList line_sizes(const RunPlan& p, uint64_t c, uint64_t& mcb, uint64_t& cmc) {
+  klf_engine* e = p.e;
+  mcb = c / klf::kCompactLines + 2;
+  // >= sum over blocks of ceil(bytes / chunk): within kCopyChunksTarget chunks unless the chunk is kCopyChunk
+  cmc = mcb + std::max<uint64_t>(p.total_bytes / klf::kCopyChunk, klf::kCopyChunksTarget) + 2;
+  return {{&e->d_line_off, (c + p.nsegs + 1) * 8}, {&e->d_meta, c * 2 + 16}, {&e->d_bits, (c / 32 + 1) * 4},
+          {&e->d_cstatus, (mcb + 1) * 3 * 8}, {&e->d_cmap, cmc * 4}, {&e->d_cseg, (mcb + 1) * 4},
+          {&e->d_mpart, (c / klf::kMatchChunk + 2) * 8}};
+}
+static hipError_t alloc_lines(const RunPlan& p, klf::RunArgs& x, uint64_t c) {
+  klf_engine* e = p.e;
+  uint64_t mcb, cmc;
+  for (auto& q : line_sizes(p, c, mcb, cmc))
+    if (const hipError_t h = q.first->ensure(q.second); h != hipSuccess) return h;
+  x.line_off = e->d_line_off.as<uint64_t>(); x.meta = e->d_meta.as<uint16_t>(); x.bits = e->d_bits.as<uint32_t>();
+  x.csum = e->d_cstatus.as<uint64_t>(); x.cmap = e->d_cmap.as<uint32_t>(); x.cseg = e->d_cseg.as<uint32_t>();
+  x.mpart = e->d_mpart.as<uint64_t>(); x.cap_lines = c; x.max_cblocks = (uint32_t)mcb; x.cmap_cap = cmc;
+  return hipSuccess;
+}
+// the slot pool: every tile where two or more lines start (16-B aligned: <= 3 spare slots each),
+// dense tiles, and the waves' partly used last chunks; an overflow reruns with what the scan reserved
+static uint64_t pool_need(const RunPlan& p, uint64_t c, uint32_t& chunk) {
+  chunk = 256;
+  if (!p.wave_pool) return p.e->pool_cap;
+  const uint64_t nwaves = (uint64_t)p.e->num_cus * 16;
+  const uint64_t per_wave = (c + 2 * p.ntiles) / nwaves;
+  while (chunk < 4096 && chunk * 4 < per_wave) chunk *= 2;
+  return std::max<uint64_t>(p.e->pool_cap, c + 3 * p.ntiles + nwaves * chunk + 1024);
+}
+// a first run's line arrays, slot pool / records and output buffer as one more allocation
+static int map_lines(RunPlan& p, const RunState& s) {
+  klf_engine* e = p.e;
+  BufList ws2;
+  if (p.out_need) ws2.push_back({&e->d_out, p.out_need});
+  if (!p.wave_pool) ws2.push_back({&e->d_slots, p.ntiles * klf::kRecStride * 4});
+  if (e->line_density == 0.0) {
+    uint64_t mcb, cmc;
+    uint32_t ch = 0;
+    for (auto& x : line_sizes(p, s.cap, mcb, cmc)) ws2.push_back(x);
+    ws2.push_back({&e->d_pool, pool_need(p, s.cap, ch) * 4});
+  }
+  HIPCHK(e, ensure_all(e->d_block2, e->block2_users, ws2), "alloc line arrays / output");
+  p.mark("line arrays / output");
+  return KLF_OK;
+}
+
+// Every RunArgs field but the line arrays (alloc_lines); launch_graph keys on the bytes: zeroed, then filled.
+static void fill_args(const RunPlan& p, const RunState& s, int attempt, klf::RunArgs& a) {
+  klf_engine* e = p.e;
+  const klf_filter* f = p.f;
+  const RunKnobs& k = p.k;
+  const bool general = p.mode == klf::CompiledSet::kGeneral, none = p.mode == klf::CompiledSet::kNone;
+  memset(static_cast<void*>(&a), 0, sizeof(a));
+  // the batch and its tile index
+  a.bytes = p.d_bytes; a.segs = e->d_segs.as<SegDesc>(); a.nsegs = p.nsegs; a.ntiles = (uint32_t)p.ntiles;
+  a.tile_seg = e->d_tile_seg.as<uint32_t>();
+  a.build_tiles = (!p.same_layout && attempt == 0) ? 1u : 0u;
+  a.tindex_wide = (p.ntiles > klf::kScanSmallTiles || k.tindex_wide) ? 1u : 0u;
+  // the filter
+  a.since_sec = f->since.sec; a.since_nsec = f->since.nsec; a.tail = f->tail;
+  since_digits(f->since.sec, f->since.nsec, a.since_dig);
+  a.grep_mode = (uint32_t)p.mode; a.match_all = e->cs.also_all ? 1u : 0u;
+  a.lit = e->d_lit.as<uint8_t>(); a.lit_words = e->d_lit.as<uint32_t>(); a.lit_len = (uint32_t)e->cs.literal.size();
+  a.lit_anchor = e->cs.literal_anchor;
+  a.lit_anchor_byte = e->cs.literal.empty() ? 0u : e->cs.literal[e->cs.literal_anchor];
+  memcpy(static_cast<void*>(&a.pats), &e->dpats, sizeof(a.pats));
+  // the workspace
+  a.tstat = e->d_tstat.as<klf::TileStat>(); a.tile_base = e->d_tile_base.as<uint64_t>(); a.bsum = e->d_bsum.as<uint64_t>();
+  a.slots = p.wave_pool ? nullptr : e->d_slots.as<uint32_t>(); a.wave_pool = p.wave_pool ? 1u : 0u;
+  a.pool = e->d_pool.as<uint32_t>(); a.pool_cap = e->pool_cap; a.pool_chunk = s.pool_chunk;
+  a.counters = e->d_counters.as<uint32_t>(); a.segout = segout_of(e);
+  a.wpre = e->d_wpre.as<uint64_t>(); a.wgrp = a.wpre + p.nsegs + 1;
+  a.out = e->d_out.as<uint8_t>(); a.out_cap = e->d_out.p ? e->d_out.cap : 0;
+  a.stage_times = (f->flags & KLF_FILTER_STAGE_TIMES) && p.evs ? 1u : 0u;
+  if (p.need_cand) { a.cand = e->d_cand.as<uint64_t>(); a.cand_cap = e->cand_cap; }
+  if (p.need_hits) {
+    a.qhits = e->d_qhits.as<uint64_t>(); a.qhits_cap = p.qhits_cap; a.hslots = e->d_hslots.as<uint16_t>();
+    a.hflat = e->d_hflat.as<uint64_t>(); a.hflat_cap = p.hflat_cap;
+  }
+  a.trec = e->d_trec.as<klf::TRec>(); a.kbase = e->d_kbase.as<uint64_t>();
+  a.truns = p.want_truns ? e->d_truns.as<uint32_t>() : nullptr;
+  a.compact_mode = p.compact_mode; a.lazy_index = p.lazy_index ? 1u : 0u;
+  a.plan_runs = (p.lazy_index && p.want_truns && p.compact_mode != 1 && k.plan_runs && !s.fuse_ok) ? 1u : 0u;
+  // windowed line index: literal patterns, and prefiltered regex sets, whose candidate lines get their bounds from
+  // k_verify; per-pattern counts too (k_fixcount's deferred lines, like k_match's fallback, ask for the whole index)
+  a.win_index = (s.win_ok &&
+                 (p.mode == klf::CompiledSet::kLiteral1 ||
+                  (general && e->cs.qf_on && !e->cs.also_all && ((e->cs.rx_count == 0 && !p.count) || k.win_index_rx))) &&
+                 k.win_index) ? 1u : 0u;
+  // no launch of kernels that would exit at once: k_match beside a working prefilter, k_tcopy before any run went dense
+  a.skip_match = (general && e->cs.qf_on && !e->cs.also_all && !s.force_match && k.skip_idle) ? 1u : 0u;
+  a.skip_tcopy = (f->tail >= 0 && !e->dense_tail_seen && p.compact_mode == 0 && k.skip_idle) ? 1u : 0u;
+  a.scatter_split = k.scatter_split;
+  // a --tail run's sparse gather without patterns: k_tailw plans a window of <= 4 compaction blocks itself (2), else
+  // k_cplan's last block runs the prefix (1); a grep run's window needs k_cplan's whole grid (0)
+  if (p.compact_mode == 1 && f->tail >= 0 && (none || k.plan_mode)) {
+    const bool index_first = !a.win_index && !p.lazy_index;
+    a.plan_mode = index_first && none &&
+                  (uint64_t)p.nsegs * ((uint64_t)f->tail + 1) <= 4ull * klf::kCompactLines ? 2u : 1u;
+    if (k.plan_mode) a.plan_mode = std::min<uint32_t>((uint32_t)atoi(k.plan_mode), index_first ? 2u : 1u);
+  }
+  if (p.count) { a.count_pats = 1; a.pcount = e->d_pcount.as<uint32_t>(); a.pairs = e->d_pairs.as<uint64_t>(); }
+  a.pairs_log2 = e->pairs_log2;
+  if (s.fuse_ok) {
+    a.fuse = 1; a.fuse_range = e->fuse_range; a.fuse_nranges = e->fuse_nranges;
+    a.fuse_ext0 = e->d_fext0.as<uint32_t>(); a.fuse_ext = e->d_fext.as<uint64_t>(); a.fuse_rinfo = e->d_frinfo.as<uint64_t>();
+  }
+}
+static int join_ac(RunPlan& p, klf::RunArgs& a) {  // the literal automaton (klf_open's thread) is read from k_tindex on
+  if (const int rc = ensure_ac(p.e); rc != KLF_OK) return rc;
+  memcpy(static_cast<void*>(&a.pats), &p.e->dpats, sizeof(a.pats));
+  p.mark("automaton");
+  return KLF_OK;
+}
+
+// One attempt: pool, arguments, launch in its shape, readback; a two-phase run may end at its first readback (phase1).
+static int launch_attempt(RunPlan& p, RunState& s, klf_result* r, int attempt, Attempt& at) {
+  klf_engine* e = p.e;
+  hipStream_t st = e->stream;
+  klf::RunArgs& a = at.a;
+  if (p.count) {
+    HIPCHK(e, e->d_pcount.ensure((size_t)p.nsegs * e->cs.n_cids * 4), "alloc pcount");
+    HIPCHK(e, e->d_pairs.ensure((size_t)8 << e->pairs_log2), "alloc pairs");
+    HIPCHK(e, hipMemsetAsync(e->d_pcount.p, 0, (size_t)p.nsegs * e->cs.n_cids * 4, st), "zero pcount");
+    HIPCHK(e, hipMemsetAsync(e->d_pairs.p, 0, (size_t)8 << e->pairs_log2, st), "zero pairs");
+  }
+  const bool two_phase = attempt == 0 && e->line_density == 0.0 && !p.density_cap && !p.small_first && !p.k.one_phase;
+  e->pool_cap = pool_need(p, s.cap, s.pool_chunk);
+  if (e->pool_cap >= (1ull << 31)) return set_err(e, KLF_EINVAL, "batch too large (line slot pool)");
+  HIPCHK(e, e->d_pool.ensure(e->pool_cap * 4), "alloc pool");
+  fill_args(p, s, attempt, a);
+  if (attempt == 0 && p.k.pool_cap) a.pool_cap = std::min<uint64_t>(a.pool_cap, p.k.pool_cap);
+  at.shape = two_phase ? "two-phase" : e->ac_pending ? "ac-split" : "plain";
+  at.ev_mask = 0; at.phase1 = at.tcopy = at.grown = false;
+  at.skip_tcopy = a.skip_tcopy; at.plan_mode = a.plan_mode; at.plan_runs = a.plan_runs;
+  r->so.resize(p.nsegs);
+  // (+ a one-pass run's extents, read back with the counters: one sync on e->stream)
+  const size_t rb_ext = a.fuse ? (size_t)e->fuse_next * 16 : 0;
+  HIPCHK(e, e->h_rb.ensure(kCtrBytes + p.nsegs * sizeof(SegOut) + rb_ext), "alloc readback");
+  const char* what = "sync phase 1";
+  if (two_phase) {
+    if (const int rc = join_ac(p, a); rc != KLF_OK) return rc;
+    a.cap_lines = 1ull << 40;  // phase 1 indexes no line array (k_tindex: no overflow, no bitmap)
+    HIPCHK(e, klf::launch_pipeline(a, st, p.evs, e->num_cus, 1, &at.ev_mask), "launch");
+    HIPCHK(e, read_back(e, p.nsegs, 0, 0, at.counters, r->so.data(), &what), what);
+    p.mark("phase 1 (launch + sync)");
+    if ((at.phase1 = at.counters[2] != 0)) return KLF_OK;  // the dense-tile pool overflowed: a whole rerun
+    learn_density(e, r->so, p.total_bytes);  // (the margin later runs size by, so that they fit)
+    // the arrays from phase 1's exact line count; a capacity clamped below it fails here, before phase 2 indexes them
+    const uint64_t need = r->so[p.nsegs - 1].line_hi + 2;
+    s.cap = std::min<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(s.cap, learned_cap(p)), need), p.k.cap_clamp);
+    if ((at.phase1 = need > s.cap)) return KLF_OK;
+    HIPCHK(e, alloc_lines(p, a, s.cap), "alloc line arrays");
+    p.mark("line arrays");
+    if (a.grep_mode != klf::CompiledSet::kNone)  // (phase 1's k_tindex zeroes it otherwise)
+      HIPCHK(e, hipMemsetAsync(a.bits, 0, (s.cap / 32 + 1) * 4, st), "zero bits");
+    HIPCHK(e, klf::launch_pipeline(a, st, p.evs, e->num_cus, 2, &at.ev_mask), "launch");
+    p.mark("phase 2 launched");
+  } else if (e->ac_pending) {  // joined while the scan runs
+    HIPCHK(e, alloc_lines(p, a, s.cap), "alloc line arrays");
+    HIPCHK(e, klf::launch_pipeline(a, st, p.evs, e->num_cus, 3, &at.ev_mask), "launch");
+    if (const int rc = join_ac(p, a); rc != KLF_OK) return rc;
+    HIPCHK(e, klf::launch_pipeline(a, st, p.evs, e->num_cus, 4, &at.ev_mask), "launch");
+  } else {
+    HIPCHK(e, alloc_lines(p, a, s.cap), "alloc line arrays");
+    p.mark("line arrays");
+    // KLF_GRAPH=1: a small batch (KLF_GRAPH_MAX_MB, default 256) replays a graph
+    const bool graph = !e->graph_off && !a.stage_times && p.total_bytes <= p.k.graph_max && p.k.graph;
+    if (graph && launch_graph(e, a, at.ev_mask, p.k.diag)) at.shape = "graph";
+    else HIPCHK(e, klf::launch_pipeline(a, st, p.evs, e->num_cus, 0, &at.ev_mask), "launch");
+  }
+  p.mark("launched");
+  what = "sync";
+  HIPCHK(e, read_back(e, p.nsegs, rb_ext, 1000 + p.total_bytes / 2000000, at.counters, r->so.data(), &what), what);
+  p.mark("pipeline done");
+  e->last_segs = p.segs;
+  if (p.k.diag)
+    fprintf(stderr, "[klf] hits=%u spilled=%u hits_over=%u nfa_queue=%u queue_over=%u deferred=%u\n",
+            at.counters[klf::kCtrVerified], at.counters[klf::kCtrHits], at.counters[klf::kCtrHitsOver],
+            at.counters[klf::kCtrQueue], at.counters[klf::kCtrQOver], at.counters[5]);
+  return KLF_OK;
+}
+static Outcome judge(const Attempt& at) {  // what a finished attempt asks for, from its counters, in this order
+  const klf::RunArgs& a = at.a; const uint32_t* c = at.counters;
+  if (at.phase1 || (c[2] & 1u)) return kLines;
+  if (a.skip_match && (c[klf::kCtrQOver] || c[klf::kCtrHitsOver])) return kMatch;
+  if (a.fuse && c[klf::kCtrFuseBad]) return kFuse;
+  if (a.win_index && c[klf::kCtrRedo]) return kIndex;
+  if (a.count_pats && c[klf::kCtrPairsOver]) return kPairs;
+  return kDone;
+}
+// changes the state as outcome `o` asks and says what follows the attempt
+static Next apply_outcome(const RunPlan& p, RunState& s, Outcome o, const Attempt& at, const std::vector<SegOut>& so) {
+  klf_engine* e = p.e; const uint32_t* c = at.counters;
+  const uint64_t need = so.back().line_hi + 2;  // (kLines: the exact line count)
+  switch (o) {
+    case kDone: return kStand;
+    case kLines:  // fails if the exact rerun overflowed too (phase 1's is not counted) or phase 1 met a clamped cap
+      if (at.phase1 ? !c[2] : s.line_reruns++ > 0) return kFail;
+      bump_pool(e, c);
+      if (at.phase1) learn_density(e, so, p.total_bytes);
+      s.cap = at.phase1 ? std::min<uint64_t>(s.cap, need) : std::min(std::max<uint64_t>(s.cap, need), p.k.cap_clamp);
+      return kRedo;
+    case kMatch: s.force_match = true; return kRedo;  // redo with k_match
+    case kFuse: s.fuse_ok = false; return kRedo;      // the two-pass rerun
+    case kIndex: s.win_ok = false; return kRedo;      // rerun with the whole index
+    case kPairs: {  // a larger set, twice at most: else the result stands without per-pattern counts
+      if (s.pair_reruns >= 2 || e->pairs_log2 >= 28) return kStand;
+      ++s.pair_reruns;  // distinct pairs <= the set's capacity + the failed inserts; size for load <= 1/2
+      const uint64_t pairs = 2 * (((uint64_t)1 << e->pairs_log2) + c[klf::kCtrPairsOver]);
+      uint32_t lg = e->pairs_log2 + 1;
+      while (lg < 28 && ((uint64_t)1 << lg) < pairs) ++lg;
+      e->pairs_log2 = lg; return kRedo;
+    }
+  }
+  return kFail;
+}
+static int deferred_tcopy(RunPlan& p, Attempt& at) {  // the dense path without its copy (skip_tcopy): launch it now
+  klf_engine* e = p.e;
+  if (!(at.a.skip_tcopy && at.counters[klf::kCtrDense])) return KLF_OK;
+  uint32_t* rb1 = e->h_rb.as<uint32_t>();
+  HIPCHK(e, klf::launch_tcopy(at.a, e->stream, nullptr, e->num_cus, nullptr), "launch tile copy");
+  HIPCHK(e, hipMemcpyAsync(rb1, e->d_counters.p, sizeof(at.counters), hipMemcpyDeviceToHost, e->stream), "D2H counters");
+  HIPCHK(e, hipStreamSynchronize(e->stream), "sync tile copy");
+  at.counters[klf::kCtrOutShort] = rb1[klf::kCtrOutShort];
+  at.a.skip_tcopy = 0; at.tcopy = true;  // (klf_retail from this run launches it)
+  return KLF_OK;
+}
+// a one-pass run's extents, in stream order (ranges ascend, and so do a range's streams)
+static void fused_extents(const RunPlan& p, klf_result* r) {
+  klf_engine* e = p.e; const uint32_t nsegs = p.nsegs;
+  r->fused = true;
+  r->fx.resize((size_t)e->fuse_next * 2);
+  memcpy(r->fx.data(), e->h_rb.as<uint8_t>() + kCtrBytes + nsegs * sizeof(SegOut), (size_t)e->fuse_next * 16);
+  r->fx_first.assign(nsegs + 1, e->fuse_next);
+  for (uint32_t q = e->fuse_nranges; q-- > 0;) {
+    const uint32_t s0 = seg_of_tile(p.segs, (uint64_t)q * e->fuse_range);
+    for (uint32_t k = e->fuse_ext0[q]; k < e->fuse_ext0[q + 1]; ++k) r->fx_first[s0 + (k - e->fuse_ext0[q])] = k;
+  }
+  uint64_t acc = 0;
+  for (uint32_t sg = 0; sg < nsegs; ++sg) {
+    r->so[sg].sel_lo = 0; r->so[sg].sel_hi = r->so[sg].since_ok;  // (every parsed line since the cutoff)
+    r->so[sg].out_lo = acc;
+    for (uint32_t k = r->fx_first[sg]; k < r->fx_first[sg + 1]; ++k) acc += r->fx[2 * (size_t)k + 1];
+    r->so[sg].out_hi = acc;
+  }
+}
+// the attempt that stands: its output (grown when short), and what the engine remembers of it
+static int publish(RunPlan& p, Attempt& at, klf_result* r) {
+  klf_engine* e = p.e; klf::RunArgs& a = at.a; const uint32_t* c = at.counters;
+  if (c[klf::kCtrOutShort]) {  // the output did not fit: grow, rerun the tail stage
+    HIPCHK(e, grow_out_retail(e, a, r->so), "grow output");
+    at.grown = true;
+    if (p.k.diag) fprintf(stderr, "[klf] output buffer grown to %zu B\n", e->d_out.cap);
+  }
+  if (a.fuse) fused_extents(p, r);
+  e->last_args = a;
+  const bool on_demand = a.lazy_index && (c[klf::kCtrDense] || a.fuse);
+  if (on_demand || a.win_index) e->index_pending.push_back(a);
+  r->index_mode = on_demand ? KLF_INDEX_ON_DEMAND : a.win_index ? KLF_INDEX_WINDOWS : KLF_INDEX_FULL;
+  r->compaction = a.fuse ? KLF_COMPACT_ONEPASS : c[klf::kCtrDense] ? KLF_COMPACT_TILES : KLF_COMPACT_GATHER;
+  e->last_gen = r->gen;
+  learn_density(e, r->so, p.total_bytes);
+  if (p.f->tail >= 0 && c[klf::kCtrDense]) e->dense_tail_seen = true;
+  return KLF_OK;
+}
+static void diag_attempt(int attempt, const Attempt& at, const char* outcome) {  // only values two processes share
+  const klf::RunArgs& a = at.a;
+  fprintf(stderr, "[klf] attempt %d %s grep_mode=%u tail=%lld cap_lines=%llu fuse=%u lazy_index=%u win_index=%u "
+          "compact_mode=%u plan_mode=%u plan_runs=%u skip_match=%u skip_tcopy=%u wave_pool=%u pool_chunk=%u "
+          "count_pats=%u build_tiles=%u -> %s%s%s\n", attempt, at.shape, a.grep_mode, (long long)a.tail,
+          (unsigned long long)a.cap_lines, a.fuse, a.lazy_index, a.win_index, a.compact_mode, at.plan_mode, at.plan_runs,
+          a.skip_match, at.skip_tcopy, a.wave_pool, a.pool_chunk, a.count_pats, a.build_tiles, outcome,
+          at.tcopy ? " +tcopy" : "", at.grown ? " +grown" : "");
+}
+// Only the event pairs this run recorded (ev_mask): another would fail the query or time an earlier run.
+// Timing is diagnostic: a recorded pair that fails to read leaves -1 in its slot and the result stands.
+static void query_timing(const RunPlan& p, klf_result* r, uint32_t ev_mask) {
+  klf_engine* e = p.e;
+  auto elapsed = [&](int k0, int k1, int slot) {
+    if (!((ev_mask >> k0 & 1u) && (ev_mask >> k1 & 1u))) return;
+    float ms = 0.f;
+    const hipError_t h = hipEventElapsedTime(&ms, e->ev[k0], e->ev[k1]);
+    r->ms[slot] = h == hipSuccess ? ms : -1.0;
+    if (h == hipSuccess) return;
+    (void)hipGetLastError();  // (the failed query's error is not the next call's)
+    if (p.k.diag) fprintf(stderr, "[klf] timing events %d/%d unreadable: %s\n", k0, k1, hipGetErrorString(h));
+  };
+  static const int kPairs[6][3] = {{1, 2, 0}, {2, 3, 1}, {3, 4, 2}, {4, 5, 3}, {0, 5, 4}, {0, 1, 5}};
+  const auto t_q0 = Clock::now();
+  for (const auto& q : kPairs) elapsed(q[0], q[1], q[2]);
+  elapsed(7, 8, 6);   // k_scan's dispatch alone
+  elapsed(9, 10, 7);  // k_tcopy's dispatch alone (dense copy)
+  if (p.k.diag)
+    fprintf(stderr, "[klf] timing queries %.1f us\n", std::chrono::duration<double, std::micro>(Clock::now() - t_q0).count());
+  r->ev_mask = ev_mask;
+}
+static void diag_summary(const RunPlan& p) {
+  const double us = std::chrono::duration<double, std::micro>(Clock::now() - p.t_run0).count();
+  fprintf(stderr, "[klf] run %.1f us: allocations %.1f us, first-batch tuning %.1f us\n", us,
+          (g_alloc_ns.load() - p.alloc0) / 1e3, p.tune_ns / 1e3);
+  std::string m = "[klf] run marks (us):";
+  auto prev = p.t_run0;
+  for (auto& x : p.marks) {
+    m += std::string(" ") + x.first + " " + std::to_string((int)std::chrono::duration<double, std::micro>(x.second - prev).count()) + ";";
+    prev = x.second;
+  }
+  fprintf(stderr, "%s\n", m.c_str());
+}
+
 static int run_device_impl(klf_engine* e, const uint8_t* d_bytes, uint32_t n_streams, const uint64_t* seg_base,
                            const uint64_t* lens, const klf_filter* f, klf_result** out) {
   if (!e || !f || !out || (n_streams && (!seg_base || !lens))) return KLF_EINVAL;
@@ -1078,681 +1692,72 @@ static int run_device_impl(klf_engine* e, const uint8_t* d_bytes, uint32_t n_str
   if (f->since.nsec < 0 || f->since.nsec >= 1000000000) return set_err(e, KLF_EINVAL, "since.nsec out of range");
   if (reinterpret_cast<uintptr_t>(d_bytes) % 16) return set_err(e, KLF_EINVAL, "device bytes must be 16-B aligned");
   *out = nullptr;
-  const auto t_run0 = std::chrono::steady_clock::now();
-  const uint64_t alloc0 = g_alloc_ns.load();
-  uint64_t tune_ns = 0;
-  // KLF_DIAG: wall-clock marks through the run (the first run's cost breakdown)
-  static const bool diag_marks = getenv("KLF_DIAG") != nullptr;
-  std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> marks;
-  auto mark = [&](const char* what) {
-    if (diag_marks) marks.emplace_back(what, std::chrono::steady_clock::now());
-  };
+  RunPlan p{e, f, d_bytes, read_knobs()};
+  RunState s;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   std::unique_ptr<klf_result> rp(new (std::nothrow) klf_result());  // freed on every error return
   klf_result* r = rp.get();
   if (!r) return KLF_ENOMEM;
-  r->e = e;
-  r->gen = ++e->gen;
-  // the contiguous copy of an earlier one-pass result (klf_result_device_out): that result
-  // is stale from here on (KLF_ESTATE), so is the copy
-  if (e->d_out2.p) e->d_out2.release();
-  r->n_streams = n_streams;
+  r->e = e; r->gen = ++e->gen; r->n_streams = n_streams;
   r->seg_of.assign(n_streams, -1);
-  if (e->cs.also_all_pending && (f->flags & KLF_FILTER_PATTERN_COUNTS)) {
-    if (const int rc = ensure_ac(e); rc != KLF_OK) return rc;
-    // the first run asking for per-pattern counts of a set with an always-pattern: compile
-    // the other patterns now (klf_open kept the set as kAll); if that fails the filter stays
-    // kAll's and the counts are reported unavailable
-    klf::CompiledSet full;
-    std::string cerr;
-    int ccode = KLF_OK;
-    if (klf::compile_set(e->pend_pats, e->pend_kinds, full, cerr, ccode, !e->tune_later, false)) {
-      e->cs = std::move(full);
-      e->dpats.n_cids = e->cs.n_cids;
-      e->dpats.n_lits = e->cs.n_lits;
-      HIPCHK(e, upload_pattern_tables(e, e->tune_later), "upload pattern tables");
-    } else {
-      e->cs.also_all_pending = false;
-      e->counts_code = ccode;
-      e->counts_err = "per-pattern counts unavailable: " + cerr;
-    }
-  }
-  auto mode = e->cs.mode;
-  // a set with an always-pattern (also_all) filters as kAll; its other patterns are
-  // evaluated only when the run counts per pattern
-  if (e->cs.also_all && !(f->flags & KLF_FILTER_PATTERN_COUNTS)) mode = klf::CompiledSet::kAll;
-  r->has_bits = mode != klf::CompiledSet::kNone;
-
-  std::vector<SegDesc> segs;
-  uint64_t total_bytes = 0, ntiles = 0, cap = 0;
-  for (uint32_t i = 0; i < n_streams; ++i) {
-    if (!lens[i]) continue;
-    if (seg_base[i] % klf::kSegAlign) return set_err(e, KLF_EINVAL, "seg_base must be 256-B aligned");
-    SegDesc d;
-    d.base = seg_base[i];
-    d.len = lens[i];
-    d.tile0 = (uint32_t)ntiles;
-    d.ntiles = (uint32_t)((lens[i] + klf::kTile - 1) / klf::kTile);
-    r->seg_of[i] = (int64_t)segs.size();
-    segs.push_back(d);
-    r->seg_base.push_back(d.base);
-    ntiles += d.ntiles;
-    total_bytes += lens[i];
-    cap += lens[i] / 32 + 2;  // kubelet lines carry a >= 31-byte prefix; overflow -> exact rerun
-  }
-  if (ntiles >= (1ull << 32)) return set_err(e, KLF_EINVAL, "batch too large");
-  const uint32_t nsegs = (uint32_t)segs.size();
-  // the line arrays: from the last run's line density (+25 %) once there is one, else the
-  // 32-B estimate above (1 G lines for 32 GiB: gigabytes of line index for a first run)
-  auto learned_cap = [&]() {
-    return (uint64_t)(e->line_density * (double)total_bytes * 1.25) + 2ull * nsegs + 4096;
-  };
-  if (e->line_density > 0.0) cap = std::min<uint64_t>(cap, learned_cap());
+  // an earlier one-pass result's contiguous copy (klf_result_device_out) is stale from here on, like that result
+  if (e->d_out2.p) e->d_out2.release();
+  int rc;
+  if (e->cs.also_all_pending && (f->flags & KLF_FILTER_PATTERN_COUNTS) && (rc = compile_pending(e)) != KLF_OK) return rc;
+  p.mode = e->cs.mode;
+  // a set with an always-pattern filters as kAll; its other patterns are evaluated only for per-pattern counts
+  if (e->cs.also_all && !(f->flags & KLF_FILTER_PATTERN_COUNTS)) p.mode = klf::CompiledSet::kAll;
+  r->has_bits = p.mode != klf::CompiledSet::kNone;
+  if ((rc = layout_segments(p, s, r, n_streams, seg_base, lens)) != KLF_OK) return rc;
   // asked-for per-pattern counts are reported even when every stream is empty (all zero)
   r->counted = (f->flags & KLF_FILTER_PATTERN_COUNTS) != 0;
   r->pcount_ok = true;  // no segment reads pcount
-  if (nsegs == 0) { e->last_gen = r->gen; *out = rp.release(); return KLF_OK; }
+  if (p.nsegs == 0) { e->last_gen = r->gen; *out = rp.release(); return KLF_OK; }
   r->pcount_ok = false;
-  // tests: a line capacity clamped on every attempt forces the overflow error below
-  uint64_t cap_clamp = ~0ull;
-  if (const char* v = getenv("KLF_DEBUG_CAP_CLAMP")) cap_clamp = std::max(1L, atol(v));
-  cap = std::min(cap, cap_clamp);
-
-  hipStream_t st = e->stream;
-  bool same_layout = segs.size() == e->last_segs.size() && e->d_tile_seg.cap >= ntiles * 4 &&
-                     memcmp(segs.data(), e->last_segs.data(), segs.size() * sizeof(SegDesc)) == 0;
-  mark("pre-segs");
-  if (!same_layout) {
-    HIPCHK(e, e->d_segs.ensure(nsegs * sizeof(SegDesc)), "alloc segs");
-    mark("segs alloc");
-    // (a pageable source: the runtime stages it before the call returns, so `segs` may go
-    // out of scope with no stream sync, which would wait for klf_open's table uploads)
-    HIPCHK(e, hipMemcpyAsync(e->d_segs.p, segs.data(), nsegs * sizeof(SegDesc), hipMemcpyHostToDevice, st),
-           "H2D segs");
-    mark("segs copy");
-    HIPCHK(e, e->d_tile_seg.ensure(ntiles * 4 + 16), "alloc tile_seg");  // + whole 16-B loads past the end
-  }
-  mark("segs");
-  // First batch of a prefiltered set: the data's own gram statistics (k_gramhist over a
-  // sample) place the needles' sampling windows.  The sample's readback is in flight while
-  // the host maps the workspace below; the layout and its upload follow the sync.  The
-  // sample's newline share also sizes the first run's line arrays (no phase-1 readback).
-  bool tune_pending = false;
-  std::chrono::steady_clock::time_point t_tune0;
-  if (mode == klf::CompiledSet::kGeneral && e->cs.qf_on && !e->cs.qf_tuned) {
-    e->cs.qf_tuned = true;
-    t_tune0 = std::chrono::steady_clock::now();
-    const char* tune = getenv("KLF_QF_TUNE");
-    if (!tune || strcmp(tune, "0") != 0) {
-      const size_t nh = klf::kGramHistWords;
-      HIPCHK(e, e->d_hist.ensure(nh * 4), "alloc hist");
-      HIPCHK(e, e->h_hist.ensure(nh * 4), "alloc hist readback");
-      HIPCHK(e, klf::launch_gramhist(d_bytes, e->d_segs.as<SegDesc>(), nsegs, klf::kGramHistSample, e->cs.qf_fold,
-                                     e->d_hist.as<uint32_t>(), st), "gram histogram");
-      HIPCHK(e, hipMemcpyAsync(e->h_hist.p, e->d_hist.p, nh * 4, hipMemcpyDeviceToHost, st), "D2H hist");
-      tune_pending = true;
-    }
-  }
-  // Any other first run (literals, no patterns, unprefiltered sets): the line density from a
-  // newline count over 64 tiles spread over the batch, read back while the workspace is
-  // mapped -- instead of a readback between the scan and the rest of the pipeline (the
-  // scan's time plus the host's array setup in series: C2's first run 1.16 ms vs 1.01 warm)
-  bool nl_pending = false;
-  uint32_t nl_blocks = 0;
-  // (a first batch whose 32-B-rule line arrays take at most ~2 GB maps them as they are: no
-  // sample, no sync before the scan -- C1 / C2; lines under 32 B overflow and rerun exactly)
-  const bool small_first = e->line_density == 0.0 && cap * 11 <= (2ull << 30) && !getenv("KLF_TWO_PHASE") &&
-                           !getenv("KLF_DEBUG_NL_SCALE");
-  if (!tune_pending && e->line_density == 0.0 && !small_first && !getenv("KLF_TWO_PHASE")) {
-    nl_blocks = (uint32_t)std::min<uint64_t>(ntiles, 64);
-    HIPCHK(e, e->d_hist.ensure((size_t)nl_blocks * 8), "alloc line sample");
-    HIPCHK(e, e->h_hist.ensure((size_t)nl_blocks * 8), "alloc line sample readback");
-    HIPCHK(e, klf::launch_nlsample(d_bytes, e->d_segs.as<SegDesc>(), nsegs, (uint32_t)ntiles, nl_blocks,
-                                   e->d_hist.as<uint32_t>(), st), "line sample");
-    HIPCHK(e, hipMemcpyAsync(e->h_hist.p, e->d_hist.p, (size_t)nl_blocks * 8, hipMemcpyDeviceToHost, st),
-           "D2H line sample");
-    nl_pending = nl_blocks > 0;
-  }
-  double est_density = 0.0;  // lines per byte of the first batch's sample (0: none)
-  auto finish_tune = [&]() -> int {
-    HIPCHK(e, hipStreamSynchronize(st), "sync hist");
-    const auto t_hist = std::chrono::steady_clock::now();
-    const uint32_t* hv = e->h_hist.as<uint32_t>();
-    klf::DataStats ds;
-    ds.bytes.assign(256, 0);
-    for (int c = 0; c < 256; ++c) {
-      ds.bytes[c] = hv[c];
-      ds.nbytes += ds.bytes[c];
-    }
-    ds.pair.assign(hv + klf::kGramHistPairs, hv + klf::kGramHistPairs + 65536);
-    for (auto& c : ds.pair) c *= 2;  // counted at every 2nd position
-    klf::stats_finish(ds);
-    if (ds.nbytes) est_density = (double)(ds.bytes['\n'] + 1) / (double)ds.nbytes;
-    klf::place_needles(e->cs, &ds);
-    const auto t_place = std::chrono::steady_clock::now();
-    if (getenv("KLF_DIAG"))
-      fprintf(stderr, "[klf] prefilter layout from %llu sampled bytes: %s\n", (unsigned long long)ds.nbytes,
-              e->cs.qf_layout.c_str());
-    HIPCHK(e, upload_prefilter(e), "upload prefilter tables");
-    if (getenv("KLF_DIAG"))
-      fprintf(stderr, "[klf] first-batch tuning: statistics %.1f us (with the workspace mapped meanwhile), layout %.1f us, uploads %.1f us\n",
-              std::chrono::duration<double, std::micro>(t_hist - t_tune0).count(),
-              std::chrono::duration<double, std::micro>(t_place - t_hist).count(),
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_place).count());
-    tune_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_tune0).count();
-    mark("first-batch tuning");
-    return KLF_OK;
-  };
-  std::vector<std::pair<DevBuf*, size_t>> ws = {
-      {&e->d_tstat, ntiles * sizeof(klf::TileStat)},
-      {&e->d_tile_base, ntiles * 8}, {&e->d_bsum, (ntiles / 1024 + 2) * 4 * 8},
-      {&e->d_counters, kCtrBytes + nsegs * sizeof(SegOut)} /* + the stream records */,
-      {&e->d_wpre, (3 * (size_t)nsegs + 2) * 8} /* + wgrp */};
-  // the dense compaction's per-tile run table (512 B per tile: 2.1 GB for 32 GiB) only for
-  // runs without a --tail limit or after a --tail run took the dense path (k_tcopy lists
-  // the runs itself without it)
-  const bool want_truns = f->tail < 0 || e->dense_tail_seen;
-  if (want_truns) ws.push_back({&e->d_truns, ntiles * klf::kRunSlots * 4});
-  uint32_t compact_mode = 0;  // tests: force either compaction path
-  if (const char* v = getenv("KLF_COMPACT")) compact_mode = !strcmp(v, "sparse") ? 1u : !strcmp(v, "dense") ? 2u : 0u;
-  // A --tail run selects at most S (N + 1) lines: up to 2^20 of them the line gather is the
-  // path (round 6; it copies any selection, long lines spread over copy chunks), so the tile
-  // copy's per-tile tables (32 B per tile: 134 MB for 32 GiB) are neither mapped nor walked
-  else if (f->tail >= 0 && (uint64_t)nsegs * ((uint64_t)f->tail + 1) <= (1ull << 20)) compact_mode = 1;
-  if (compact_mode != 1) {
-    ws.push_back({&e->d_trec, ntiles * sizeof(klf::TRec)});
-    ws.push_back({&e->d_kbase, ntiles * 16});
-  }
-  // One-pass compaction (no patterns, --tail -1): the fused scan compacts each wave's tile
-  // range in place.  The ranges (a multiple of kScanGroup tiles each, one per wave of a
-  // full-occupancy launch) and each range's first extent (one extent per stream it touches).
-  const bool fuse_try = mode == klf::CompiledSet::kNone && f->tail < 0 && compact_mode == 0 &&
-                        !(getenv("KLF_FUSE") && !strcmp(getenv("KLF_FUSE"), "0"));
-  bool fuse_ok = fuse_try;
-  uint64_t seg_end = 0;  // past the last input byte (the fused output is laid out like the input)
-  for (const auto& d : segs) seg_end = std::max<uint64_t>(seg_end, d.base + d.len);
-  auto seg_of_tile = [&](uint64_t t) -> uint32_t {
-    uint32_t lo = 0, hi = nsegs;  // the last segment whose tile0 <= t
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) / 2;
-      if (segs[mid].tile0 <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-  };
-  if (fuse_try) {
-    const uint64_t waves = (uint64_t)std::max(1, klf::fuse_waves(e->num_cus));
-    uint64_t R = (ntiles + waves - 1) / waves;
-    R = (R + klf::kScanGroup - 1) / klf::kScanGroup * klf::kScanGroup;
-    if (const char* v = getenv("KLF_DEBUG_FUSE_RANGE"))  // tests: short ranges (many range seams)
-      R = std::max<uint64_t>(klf::kScanGroup, (uint64_t)atol(v) / klf::kScanGroup * klf::kScanGroup);
-    const uint32_t nr = (uint32_t)((ntiles + R - 1) / R);
-    const bool same_fuse_layout = segs.size() == e->fuse_segs.size() &&
-                                  memcmp(segs.data(), e->fuse_segs.data(), segs.size() * sizeof(SegDesc)) == 0;
-    if (!same_fuse_layout || e->fuse_range != (uint32_t)R || e->fuse_nranges != nr) {
-      e->fuse_segs.clear();  // (invalid until the table below is on its way)
-      e->fuse_ext0.assign(nr + 1, 0);
-      for (uint32_t q = 0; q < nr; ++q) {
-        const uint64_t t0 = (uint64_t)q * R, t1 = std::min<uint64_t>(t0 + R, ntiles) - 1;
-        e->fuse_ext0[q + 1] = e->fuse_ext0[q] + (seg_of_tile(t1) - seg_of_tile(t0) + 1);
-      }
-      HIPCHK(e, e->d_fext0.ensure((nr + 1) * 4), "alloc fuse ranges");
-      HIPCHK(e, hipMemcpyAsync(e->d_fext0.p, e->fuse_ext0.data(), (nr + 1) * 4, hipMemcpyHostToDevice, st),
-             "H2D fuse ranges");
-      e->fuse_range = (uint32_t)R;
-      e->fuse_nranges = nr;
-      e->fuse_next = e->fuse_ext0[nr];
-      e->fuse_segs = segs;
-    }
-    HIPCHK(e, e->d_fext.ensure((size_t)e->fuse_next * 16), "alloc fuse extents");
-    HIPCHK(e, e->d_frinfo.ensure((size_t)e->fuse_nranges * 32), "alloc fuse range states");
-  }
+  plan_run(p, s);
+  double est_density = 0.0;
+  if ((rc = upload_layout(p)) != KLF_OK) return rc;
+  if ((rc = start_sample(p)) != KLF_OK) return rc;  // (its readback is in flight while the workspace is mapped)
+  if (p.fuse_try && (rc = fuse_ranges(p)) != KLF_OK) return rc;
   e->index_pending.clear();
-  // lazy line index (grep none, --tail -1; KLF_LAZY_INDEX=0 turns it off)
-  const bool full_index = (f->flags & KLF_FILTER_FULL_INDEX) != 0;
-  // KLF_FILTER_NO_TIMING: no event in the launch sequence (launch_pipeline records none)
-  hipEvent_t* const evs = (f->flags & KLF_FILTER_NO_TIMING) ? nullptr : e->ev;
-  const bool lazy_index = mode == klf::CompiledSet::kNone && f->tail < 0 && !full_index &&
-                          !(getenv("KLF_LAZY_INDEX") && !strcmp(getenv("KLF_LAZY_INDEX"), "0"));
-  // (a run that needs every line's index -- k_match's fallback -- turns it off)
-  bool win_ok = !full_index;
-  // The output buffer: sized for the whole input up front when the run keeps about as much
-  // as it reads (no --tail limit: C3-like), else grown
-  // on demand -- the compaction skips a copy that would not fit, the host grows the buffer
-  // to the run's output and reruns the tail stage (first runs only: the buffer is kept).
-  // A --tail run then never maps an input-sized buffer (34 GB for C4 / C5).
-  uint64_t out_need = 0;  // the output buffer (mapped below, with a first run's line arrays)
-  if (f->tail < 0) out_need = std::max<uint64_t>(total_bytes, fuse_try ? seg_end : 0) + 64;
-  else if (!e->d_out.p) {  // a first --tail run: room for a typical tail window (no rerun to grow)
-    uint64_t first = 64ull << 20;
-    if (const char* v = getenv("KLF_DEBUG_OUT_INIT")) first = (uint64_t)std::max(1L, atol(v));  // tests: force growth
-    out_need = std::min<uint64_t>(total_bytes + 64, first);
+  if ((rc = map_workspace(p)) != KLF_OK) return rc;
+  if ((rc = finish_sample(p, est_density)) != KLF_OK) return rc;
+  plan_density(p, s, est_density);
+  if ((rc = map_lines(p, s)) != KLF_OK) return rc;
+  // each attempt launches the whole run and reads its counters back; apply_outcome changes the state for a redo
+  Attempt at;
+  Outcome o = kDone;
+  Next next = kRedo;
+  for (int attempt = 0; attempt < 4 && next == kRedo; ++attempt) {
+    if ((rc = launch_attempt(p, s, r, attempt, at)) != KLF_OK) return rc;
+    o = judge(at);
+    if (o != kLines && o != kMatch && (rc = deferred_tcopy(p, at)) != KLF_OK) return rc;
+    next = apply_outcome(p, s, o, at, r->so);
+    if (next == kStand && (rc = publish(p, at, r)) != KLF_OK) return rc;
+    if (p.k.diag) diag_attempt(attempt, at, kOutcomeName[next == kStand ? kDone : o]);
   }
-  const bool need_cand = mode == klf::CompiledSet::kGeneral && e->cs.qf_on && e->cs.rx_count;
-  if (need_cand) ws.push_back({&e->d_cand, (size_t)e->cand_cap * 16});
-  const bool need_hits = mode == klf::CompiledSet::kGeneral && e->cs.qf_on;
-  // bitmap hits: < 1 per 8 KiB tile on log text (C4's 1,024 literals: 0.41, C5 0.02),
-  // kHitSlots per tile recorded in place; spills beyond 1 per 8 KiB of input -> k_match decides
-  const uint32_t qhits_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(total_bytes / 8192, 1u << 16),
-                                                          e->hits_cap_max);
-  // flattened hit slots: up to 1 per 4 KiB of input (2 per tile); more -> k_match decides
-  // (round 5 mapped 1 per 512 B: 537 MB for 32 GiB, in every first run's workspace)
-  const uint64_t hflat_cap = std::min<uint64_t>(std::max<uint64_t>(total_bytes / 4096, 1u << 20),
-                                                (uint64_t)ntiles * klf::kHitSlots);
-  if (need_hits) {
-    ws.push_back({&e->d_qhits, (size_t)qhits_cap * 8});
-    ws.push_back({&e->d_hslots, (size_t)ntiles * klf::kHitSlots * 2});
-    ws.push_back({&e->d_hflat, (size_t)hflat_cap * 8});
-  }
-  HIPCHK(e, ensure_all(e->d_block, e->block_users, ws), "alloc workspace");
-
-  const bool count = (f->flags & KLF_FILTER_PATTERN_COUNTS) && mode == klf::CompiledSet::kGeneral && e->cs.n_cids;
-  r->counted = (f->flags & KLF_FILTER_PATTERN_COUNTS) != 0;
-  mark("workspace");
-  if (tune_pending) {
-    const int rc = finish_tune();
-    if (rc != KLF_OK) return rc;
-  }
-  if (nl_pending) {
-    HIPCHK(e, hipStreamSynchronize(st), "sync line sample");
-    const uint32_t* hv = e->h_hist.as<uint32_t>();
-    uint64_t nl = 0, nb = 0;
-    for (uint32_t b = 0; b < nl_blocks; ++b) { nl += hv[2 * b]; nb += hv[2 * b + 1]; }
-    if (nb) est_density = (double)(nl + nl_blocks) / (double)nb;  // (+1 per tile: a margin, never 0)
-    if (const char* v = getenv("KLF_DEBUG_NL_SCALE")) est_density *= atof(v);  // tests: force an underestimate
-    mark("line sample");
-  }
-  // a first run with the sample's line density: the line arrays from it (x2 + a margin:
-  // an overflow reruns with exact sizes), in one launch phase
-  const bool density_cap = e->line_density == 0.0 && est_density > 0.0 && !getenv("KLF_TWO_PHASE");
-  // Where the scan keeps the slots of tiles with two or more line starts (round 6): long lines
-  // (under one per KiB: C5) -> per-wave chunks of the pool, no record regions allocated at all
-  // (C5 k_scan -1.4 %, cold 8.6 -> 8.3 ms); shorter lines -> the per-tile record regions,
-  // 1,152 B per tile, written as whole lines (C2 / C3 / C4 ran 0.7-1.5 % faster on them,
-  // r6g).  KLF_WAVE_POOL=1 / 0 forces either.
-  const double dens = e->line_density > 0.0 ? e->line_density : est_density;
-  const char* wpv = getenv("KLF_WAVE_POOL");
-  const bool wave_pool = wpv ? strcmp(wpv, "0") != 0 : (dens > 0.0 && dens * 1024.0 < 1.0);
-  if (density_cap)
-    cap = std::min<uint64_t>(cap, (uint64_t)(est_density * (double)total_bytes * 2.0) + 2ull * nsegs + 65536);
-  // the buffers indexed by global line (and the compaction's per-block tables) for capacity c
-  auto line_sizes = [&](uint64_t c) {
-    const uint64_t mcb = c / klf::kCompactLines + 2;
-    // >= sum over blocks of ceil(bytes / chunk) (>= 1 each): the block prefix's chunk keeps
-    // the output within kCopyChunksTarget chunks unless it is the largest, kCopyChunk
-    const uint64_t cmc = mcb + std::max<uint64_t>(total_bytes / klf::kCopyChunk, klf::kCopyChunksTarget) + 2;
-    return std::vector<std::pair<DevBuf*, size_t>>{
-        {&e->d_line_off, (c + nsegs + 1) * 8}, {&e->d_meta, c * 2 + 16}, {&e->d_bits, (c / 32 + 1) * 4},
-        {&e->d_cstatus, (mcb + 1) * 3 * 8}, {&e->d_cmap, cmc * 4}, {&e->d_cseg, (mcb + 1) * 4},
-        {&e->d_mpart, (c / klf::kMatchChunk + 2) * 8}};
-  };
-  auto pool_need = [&](uint64_t c, uint32_t& chunk) -> uint64_t {  // the slot pool (wave_pool: see the scan)
-    chunk = 256;
-    if (!wave_pool) return e->pool_cap;
-    const uint64_t nwaves = (uint64_t)e->num_cus * 16;
-    const uint64_t per_wave = (c + 2 * ntiles) / nwaves;
-    while (chunk < 4096 && chunk * 4 < per_wave) chunk *= 2;
-    return std::max<uint64_t>(e->pool_cap, c + 3 * ntiles + nwaves * chunk + 1024);
-  };
-  {
-    // A first run maps its line arrays, slot pool / records and output buffer as one more
-    // allocation, now that their sizes are known (each hipMalloc costs 1-26 us of host time
-    // with the GPU idle: ~10 of them per first run); later runs grow single buffers
-    std::vector<std::pair<DevBuf*, size_t>> ws2;
-    if (out_need) ws2.push_back({&e->d_out, out_need});
-    if (!wave_pool) ws2.push_back({&e->d_slots, ntiles * klf::kRecStride * 4});
-    if (e->line_density == 0.0) {
-      for (auto& x : line_sizes(cap)) ws2.push_back(x);
-      uint32_t ch = 0;
-      ws2.push_back({&e->d_pool, pool_need(cap, ch) * 4});
-    }
-    HIPCHK(e, ensure_all(e->d_block2, e->block2_users, ws2), "alloc line arrays / output");
-    mark("line arrays / output");
-  }
-  uint32_t pool_chunk = 256;  // (per attempt, below: the wave pool's chunk size)
-  bool force_match = false;   // an overflowed hit list / NFA queue: redo the run with k_match
-  // every RunArgs field but the line arrays (alloc_lines) of a run over the whole batch
-  auto fill_args = [&](klf::RunArgs& a, int attempt) {
-    memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.bytes = d_bytes;
-    a.segs = e->d_segs.as<SegDesc>();
-    a.nsegs = nsegs;
-    a.ntiles = (uint32_t)ntiles;
-    a.tile_seg = e->d_tile_seg.as<uint32_t>();
-    a.build_tiles = (!same_layout && attempt == 0) ? 1u : 0u;
-    // tests: KLF_DEBUG_TINDEX_WIDE=1 runs the large-batch tile index on any batch
-    a.tindex_wide = (ntiles > klf::kScanSmallTiles || getenv("KLF_DEBUG_TINDEX_WIDE")) ? 1u : 0u;
-    a.since_sec = f->since.sec;
-    a.since_nsec = f->since.nsec;
-    since_digits(f->since.sec, f->since.nsec, a.since_dig);
-    a.tail = f->tail;
-    a.grep_mode = (uint32_t)mode;
-    a.match_all = e->cs.also_all ? 1u : 0u;
-    a.lit = e->d_lit.as<uint8_t>();
-    a.lit_len = (uint32_t)e->cs.literal.size();
-    a.lit_anchor = e->cs.literal_anchor;
-    a.lit_anchor_byte = e->cs.literal.empty() ? 0u : e->cs.literal[e->cs.literal_anchor];
-    a.lit_words = e->d_lit.as<uint32_t>();
-    memcpy(static_cast<void*>(&a.pats), &e->dpats, sizeof(a.pats));
-    a.tstat = e->d_tstat.as<klf::TileStat>();
-    a.slots = wave_pool ? nullptr : e->d_slots.as<uint32_t>();
-    a.pool = e->d_pool.as<uint32_t>();
-    a.pool_cap = e->pool_cap;
-    a.wave_pool = wave_pool ? 1u : 0u;
-    a.pool_chunk = pool_chunk;
-    a.tile_base = e->d_tile_base.as<uint64_t>();
-    a.bsum = e->d_bsum.as<uint64_t>();
-    a.counters = e->d_counters.as<uint32_t>();
-    a.segout = segout_of(e);
-    a.wpre = e->d_wpre.as<uint64_t>();
-    a.wgrp = a.wpre + nsegs + 1;
-    a.out = e->d_out.as<uint8_t>();
-    a.out_cap = e->d_out.p ? e->d_out.cap : 0;
-    a.stage_times = (f->flags & KLF_FILTER_STAGE_TIMES) && evs ? 1u : 0u;
-    a.cand = need_cand ? e->d_cand.as<uint64_t>() : nullptr;
-    a.cand_cap = need_cand ? e->cand_cap : 0;
-    a.qhits = need_hits ? e->d_qhits.as<uint64_t>() : nullptr;
-    a.hslots = need_hits ? e->d_hslots.as<uint16_t>() : nullptr;
-    a.hflat = need_hits ? e->d_hflat.as<uint64_t>() : nullptr;
-    a.hflat_cap = need_hits ? hflat_cap : 0;
-    a.qhits_cap = need_hits ? qhits_cap : 0;
-    a.trec = e->d_trec.as<klf::TRec>();
-    a.truns = want_truns ? e->d_truns.as<uint32_t>() : nullptr;
-    a.kbase = e->d_kbase.as<uint64_t>();
-    a.compact_mode = compact_mode;
-    a.lazy_index = lazy_index ? 1u : 0u;
-    a.plan_runs = (lazy_index && want_truns && compact_mode != 1 &&
-                   !(getenv("KLF_PLAN_RUNS") && !strcmp(getenv("KLF_PLAN_RUNS"), "0"))) ? 1u : 0u;
-    // windowed line index: literal patterns, and (round 6) prefiltered regex sets, whose
-    // candidate lines get their bounds from k_verify; per-pattern counts too (k_fixcount's
-    // deferred lines, like k_match's fallback, ask for a rerun with the whole index)
-    const bool win_rx = !(getenv("KLF_WIN_INDEX_RX") && !strcmp(getenv("KLF_WIN_INDEX_RX"), "0"));
-    a.win_index = (win_ok &&
-                   (mode == klf::CompiledSet::kLiteral1 ||
-                    (mode == klf::CompiledSet::kGeneral && e->cs.qf_on && !e->cs.also_all &&
-                     ((e->cs.rx_count == 0 && !count) || win_rx))) &&
-                   !(getenv("KLF_WIN_INDEX") && !strcmp(getenv("KLF_WIN_INDEX"), "0"))) ? 1u : 0u;
-    a.scatter_mode = 0;
-    // no launch of kernels that would exit at once (each costs ~4 us plus its boundary):
-    // k_match beside a working prefilter, k_tcopy in a --tail run before any went dense
-    a.skip_match = (mode == klf::CompiledSet::kGeneral && e->cs.qf_on && !e->cs.also_all && !force_match &&
-                    !(getenv("KLF_SKIP_IDLE") && !strcmp(getenv("KLF_SKIP_IDLE"), "0"))) ? 1u : 0u;
-    a.skip_tcopy = (f->tail >= 0 && !e->dense_tail_seen && compact_mode == 0 &&
-                    !(getenv("KLF_SKIP_IDLE") && !strcmp(getenv("KLF_SKIP_IDLE"), "0"))) ? 1u : 0u;
-    // waves per scatter group (0: k_scatter picks it from its grid; tests force a split)
-    a.scatter_split = getenv("KLF_SCATTER_SPLIT") ? (uint32_t)std::max(0L, atol(getenv("KLF_SCATTER_SPLIT"))) : 0u;
-    // a --tail run's sparse gather with fewer launches (RunArgs::plan_mode), without patterns
-    // (a window of at most S (N + 1) lines, the line index built before k_tailw): k_tailw
-    // plans a window of at most 4 compaction blocks itself (C1: k_tailw +4.7 us for k_cplan
-    // 4.8 + k_cmid 5.0), else k_cplan's last block runs the prefix (7.5 us).  A grep run's
-    // window spans every line between its N + 1 matches: its block sums need k_cplan's
-    // whole grid (C5 with the prefix in k_cplan's last block: 15.9 -> 24.1 us, r6t).
-    // (KLF_PLAN_MODE=0 / 1 / 2 forces one, tests)
-    a.plan_mode = 0;
-    if (compact_mode == 1 && f->tail >= 0 && (mode == klf::CompiledSet::kNone || getenv("KLF_PLAN_MODE"))) {
-      const bool index_first = !a.win_index && !lazy_index;
-      a.plan_mode = index_first && mode == klf::CompiledSet::kNone &&
-                    (uint64_t)nsegs * ((uint64_t)f->tail + 1) <= 4ull * klf::kCompactLines ? 2u : 1u;
-      if (const char* v = getenv("KLF_PLAN_MODE")) a.plan_mode = std::min<uint32_t>((uint32_t)atoi(v), index_first ? 2u : 1u);
-    }
-    a.count_pats = count ? 1u : 0u;
-    a.pcount = count ? e->d_pcount.as<uint32_t>() : nullptr;
-    a.pairs = count ? e->d_pairs.as<uint64_t>() : nullptr;
-    a.pairs_log2 = e->pairs_log2;
-    if (fuse_ok) {
-      a.fuse = 1;
-      a.plan_runs = 0;
-      a.fuse_range = e->fuse_range;
-      a.fuse_nranges = e->fuse_nranges;
-      a.fuse_ext0 = e->d_fext0.as<uint32_t>();
-      a.fuse_ext = e->d_fext.as<uint64_t>();
-      a.fuse_rinfo = e->d_frinfo.as<uint64_t>();
-    }
-  };
-  bool overflow = false, pairs_over = false;
-  uint32_t ev_mask = 0;
-  const bool graph_on = getenv("KLF_GRAPH") && strcmp(getenv("KLF_GRAPH"), "0") != 0;  // (opt-in)
-  const uint64_t graph_max = (getenv("KLF_GRAPH_MAX_MB") ? (uint64_t)std::max(0L, atol(getenv("KLF_GRAPH_MAX_MB"))) : 256ull) << 20;
-  for (int attempt = 0, line_reruns = 0, pair_reruns = 0; attempt < 4; ++attempt) {
-    if (count) {
-      HIPCHK(e, e->d_pcount.ensure((size_t)nsegs * e->cs.n_cids * 4), "alloc pcount");
-      HIPCHK(e, e->d_pairs.ensure((size_t)8 << e->pairs_log2), "alloc pairs");
-      HIPCHK(e, hipMemsetAsync(e->d_pcount.p, 0, (size_t)nsegs * e->cs.n_cids * 4, st), "zero pcount");
-      HIPCHK(e, hipMemsetAsync(e->d_pairs.p, 0, (size_t)8 << e->pairs_log2, st), "zero pairs");
-    }
-    // An engine's first run sizes its line arrays from its own line count: the pipeline
-    // runs up to the tile index, the count is read back, the arrays are allocated, the
-    // rest follows (one extra sync, first runs only).
-    const bool two_phase = attempt == 0 && e->line_density == 0.0 && !density_cap && !small_first && !getenv("KLF_ONE_PHASE");
-    // the arrays indexed by global line (and the compaction's per-block tables)
-    auto alloc_lines = [&](klf::RunArgs& x, uint64_t c) -> hipError_t {
-      const uint64_t mcb = c / klf::kCompactLines + 2;
-      const uint64_t cmc = mcb + std::max<uint64_t>(total_bytes / klf::kCopyChunk, klf::kCopyChunksTarget) + 2;
-      hipError_t h;
-      for (auto& q : line_sizes(c))
-        if ((h = q.first->ensure(q.second)) != hipSuccess) return h;
-      x.line_off = e->d_line_off.as<uint64_t>();
-      x.meta = e->d_meta.as<uint16_t>();
-      x.bits = e->d_bits.as<uint32_t>();
-      x.csum = e->d_cstatus.as<uint64_t>();
-      x.cmap = e->d_cmap.as<uint32_t>();
-      x.cmap_cap = cmc;
-      x.cseg = e->d_cseg.as<uint32_t>();
-      x.mpart = e->d_mpart.as<uint64_t>();
-      x.cap_lines = c;
-      x.max_cblocks = (uint32_t)mcb;
-      return hipSuccess;
-    };
-    // the pool: every tile where two or more lines start (16-B aligned: <= 3 spare slots each),
-    // dense tiles, and the waves' partly used last chunks (wave_pool); an overflow reruns
-    // with the count the scan reserved
-    e->pool_cap = pool_need(cap, pool_chunk);
-    if (e->pool_cap >= (1ull << 31)) return set_err(e, KLF_EINVAL, "batch too large (line slot pool)");
-    HIPCHK(e, e->d_pool.ensure(e->pool_cap * 4), "alloc pool");
-    klf::RunArgs a;
-    fill_args(a, attempt);
-    if (attempt == 0 && getenv("KLF_DEBUG_POOL_CAP"))  // tests: a first attempt whose pool overflows
-      a.pool_cap = std::min<uint64_t>(a.pool_cap, (uint64_t)std::max(1L, atol(getenv("KLF_DEBUG_POOL_CAP"))));
-    ev_mask = 0;  // the events this attempt records (the timing queries read only those)
-    r->so.resize(nsegs);
-    uint32_t counters[32];
-    // (+ a one-pass run's extents, read back with the counters: one sync on e->stream)
-    const size_t rb_ext = fuse_ok ? (size_t)e->fuse_next * 16 : 0;
-    HIPCHK(e, e->h_rb.ensure(kCtrBytes + nsegs * sizeof(SegOut) + rb_ext), "alloc readback");
-    // the literal automaton (klf_open's thread) is read from k_tindex on (deferred lines)
-    auto join_ac = [&]() -> int {
-      if (const int rc = ensure_ac(e); rc != KLF_OK) return rc;
-      memcpy(static_cast<void*>(&a.pats), &e->dpats, sizeof(a.pats));
-      mark("automaton");
-      return KLF_OK;
-    };
-    if (two_phase) {
-      if (const int rc = join_ac(); rc != KLF_OK) return rc;
-      a.cap_lines = 1ull << 40;  // phase 1 indexes no line array (k_tindex: no overflow, no bitmap)
-      HIPCHK(e, klf::launch_pipeline(a, st, evs, e->num_cus, 1, &ev_mask), "launch");
-      uint8_t* rb1 = e->h_rb.as<uint8_t>();
-      HIPCHK(e, hipMemcpyAsync(rb1, e->d_counters.p, kCtrBytes + nsegs * sizeof(SegOut), hipMemcpyDeviceToHost, st),
-             "D2H counters + records");
-      HIPCHK(e, hipStreamSynchronize(st), "sync phase 1");
-      mark("phase 1 (launch + sync)");
-      memcpy(counters, rb1, sizeof(counters));
-      memcpy(r->so.data(), rb1 + kCtrBytes, nsegs * sizeof(SegOut));
-      if (counters[2]) {  // the dense-tile pool overflowed: a whole rerun (as below)
-        e->pool_cap = std::max<uint64_t>(e->pool_cap, (uint64_t)counters[klf::kCtrPool] + (uint64_t)e->num_cus * 16 * 4096);
-        e->line_density = (double)(r->so[nsegs - 1].line_hi + 1) / (double)total_bytes;
-        cap = std::min<uint64_t>(cap, r->so[nsegs - 1].line_hi + 2);
-        continue;
-      }
-      // the same margin later runs size by (their line density estimate), so that they fit
-      e->line_density = (double)(r->so[nsegs - 1].line_hi + 1) / (double)total_bytes;
-      // phase 1 knows the exact line count: size the arrays to it (the 32-B estimate is
-      // short for lines under 32 B); a capacity still below it (only KLF_DEBUG_CAP_CLAMP)
-      // fails here, before phase 2's kernels index the arrays (advisor r03)
-      const uint64_t need = r->so[nsegs - 1].line_hi + 2;
-      cap = std::min<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(cap, learned_cap()), need), cap_clamp);
-      if (need > cap) {
-        overflow = true;
-        break;
-      }
-      HIPCHK(e, alloc_lines(a, cap), "alloc line arrays");
-      mark("line arrays");
-      if (a.grep_mode != klf::CompiledSet::kNone)  // (phase 1's k_tindex zeroes it otherwise)
-        HIPCHK(e, hipMemsetAsync(a.bits, 0, (cap / 32 + 1) * 4, st), "zero bits");
-      HIPCHK(e, klf::launch_pipeline(a, st, evs, e->num_cus, 2, &ev_mask), "launch");
-      mark("phase 2 launched");
-    } else if (e->ac_pending) {  // joined while the scan runs
-      HIPCHK(e, alloc_lines(a, cap), "alloc line arrays");
-      HIPCHK(e, klf::launch_pipeline(a, st, evs, e->num_cus, 3, &ev_mask), "launch");
-      if (const int rc = join_ac(); rc != KLF_OK) return rc;
-      HIPCHK(e, klf::launch_pipeline(a, st, evs, e->num_cus, 4, &ev_mask), "launch");
-    } else {
-      HIPCHK(e, alloc_lines(a, cap), "alloc line arrays");
-      mark("line arrays");
-      // KLF_GRAPH=1: a small batch (KLF_GRAPH_MAX_MB, default 256) replays a graph
-      const bool graph = !e->graph_off && !a.stage_times && total_bytes <= graph_max && graph_on;
-      if (!(graph && launch_graph(e, a, ev_mask)))
-        HIPCHK(e, klf::launch_pipeline(a, st, evs, e->num_cus, 0, &ev_mask), "launch");
-    }
-    mark("launched");
-    uint8_t* rb = e->h_rb.as<uint8_t>();
-    HIPCHK(e, hipMemcpyAsync(rb, e->d_counters.p, kCtrBytes + nsegs * sizeof(SegOut), hipMemcpyDeviceToHost, st),
-           "D2H counters + records");
-    if (a.fuse)
-      HIPCHK(e, hipMemcpyAsync(rb + kCtrBytes + nsegs * sizeof(SegOut), e->d_fext.p, rb_ext,
-                               hipMemcpyDeviceToHost, st), "D2H extents");
-    HIPCHK(e, wait_stream(st, 1000 + total_bytes / 2000000), "sync");
-    mark("pipeline done");
-    memcpy(counters, rb, sizeof(counters));
-    memcpy(r->so.data(), rb + kCtrBytes, nsegs * sizeof(SegOut));
-    e->last_segs = segs;
-    if (getenv("KLF_DIAG"))
-      fprintf(stderr, "[klf] hits=%u spilled=%u hits_over=%u nfa_queue=%u queue_over=%u deferred=%u\n",
-              counters[klf::kCtrVerified], counters[klf::kCtrHits], counters[klf::kCtrHitsOver],
-              counters[klf::kCtrQueue], counters[klf::kCtrQOver], counters[5]);
-    overflow = (counters[2] & 1u) != 0;
-    if (overflow) {  // more lines (or dense-tile slots) than estimated: rerun with exact sizes
-      if (line_reruns++) break;
-      cap = std::min(std::max<uint64_t>(cap, r->so[nsegs - 1].line_hi + 2), cap_clamp);
-      e->pool_cap = std::max<uint64_t>(e->pool_cap, (uint64_t)counters[klf::kCtrPool] + (uint64_t)e->num_cus * 16 * 4096);
-      continue;
-    }
-    if (a.skip_match && (counters[klf::kCtrQOver] || counters[klf::kCtrHitsOver])) {  // k_match decides: redo with it
-      force_match = true;
-      continue;
-    }
-    if (a.skip_tcopy && counters[klf::kCtrDense]) {  // the dense path without its copy: launch it now
-      uint32_t* rb1 = e->h_rb.as<uint32_t>();
-      HIPCHK(e, klf::launch_tcopy(a, st, nullptr, e->num_cus, nullptr), "launch tile copy");
-      HIPCHK(e, hipMemcpyAsync(rb1, e->d_counters.p, sizeof(counters), hipMemcpyDeviceToHost, st), "D2H counters");
-      HIPCHK(e, hipStreamSynchronize(st), "sync tile copy");
-      counters[klf::kCtrOutShort] = rb1[klf::kCtrOutShort];
-      a.skip_tcopy = 0;  // (klf_retail from this run launches it)
-    }
-    if (a.fuse && counters[klf::kCtrFuseBad]) {  // a deferred line or a dense tile: the two-pass rerun
-      fuse_ok = false;
-      continue;
-    }
-    if (a.win_index && counters[klf::kCtrRedo]) {  // k_match needed the whole index: rerun with it
-      win_ok = false;
-      continue;
-    }
-    pairs_over = count && counters[klf::kCtrPairsOver] != 0;
-    if (pairs_over && pair_reruns < 2 && e->pairs_log2 < 28) {  // the pair set filled: a larger one
-      // distinct pairs <= the set's capacity + the failed inserts; size for load <= 1/2
-      ++pair_reruns;
-      const uint64_t need = 2 * (((uint64_t)1 << e->pairs_log2) + counters[klf::kCtrPairsOver]);
-      uint32_t lg = e->pairs_log2 + 1;
-      while (lg < 28 && ((uint64_t)1 << lg) < need) ++lg;
-      e->pairs_log2 = lg;
-      continue;
-    }
-    if (counters[klf::kCtrOutShort]) {  // the output did not fit: grow, rerun the tail stage
-      HIPCHK(e, grow_out_retail(e, a, r->so), "grow output");
-      if (getenv("KLF_DIAG")) fprintf(stderr, "[klf] output buffer grown to %zu B\n", e->d_out.cap);
-    }
-    if (a.fuse) {  // the extents, in stream order (ranges ascend, and so do a range's streams)
-      r->fused = true;
-      r->fx.resize((size_t)e->fuse_next * 2);
-      memcpy(r->fx.data(), rb + kCtrBytes + nsegs * sizeof(SegOut), (size_t)e->fuse_next * 16);
-      r->fx_first.assign(nsegs + 1, e->fuse_next);
-      for (uint32_t q = e->fuse_nranges; q-- > 0;) {
-        const uint32_t s0 = seg_of_tile((uint64_t)q * e->fuse_range);
-        for (uint32_t k = e->fuse_ext0[q]; k < e->fuse_ext0[q + 1]; ++k) r->fx_first[s0 + (k - e->fuse_ext0[q])] = k;
-      }
-      uint64_t acc = 0;
-      for (uint32_t sg = 0; sg < nsegs; ++sg) {
-        r->so[sg].sel_lo = 0;  // --tail -1, no patterns: every parsed line since the cutoff
-        r->so[sg].sel_hi = r->so[sg].since_ok;
-        r->so[sg].out_lo = acc;
-        for (uint32_t k = r->fx_first[sg]; k < r->fx_first[sg + 1]; ++k) acc += r->fx[2 * (size_t)k + 1];
-        r->so[sg].out_hi = acc;
-      }
-    }
-    e->last_args = a;
-    const bool on_demand = a.lazy_index && (counters[klf::kCtrDense] || a.fuse);
-    if (on_demand || a.win_index) e->index_pending.push_back(a);
-    r->index_mode = on_demand ? KLF_INDEX_ON_DEMAND : a.win_index ? KLF_INDEX_WINDOWS : KLF_INDEX_FULL;
-    r->compaction = a.fuse ? KLF_COMPACT_ONEPASS : counters[klf::kCtrDense] ? KLF_COMPACT_TILES : KLF_COMPACT_GATHER;
-    e->last_gen = r->gen;
-    e->line_density = (double)(r->so[nsegs - 1].line_hi + 1) / (double)total_bytes;
-    if (f->tail >= 0 && counters[klf::kCtrDense]) e->dense_tail_seen = true;
-    break;
-  }
-  if (count && !overflow && !pairs_over) {
-    r->pcount.resize((size_t)nsegs * e->cs.n_cids);
+  if (p.count && next == kStand && o != kPairs) {
+    r->pcount.resize((size_t)p.nsegs * e->cs.n_cids);
     HIPCHK(e, hipMemcpy(r->pcount.data(), e->d_pcount.p, r->pcount.size() * 4, hipMemcpyDeviceToHost), "D2H pcount");
     r->pcount_ok = true;
   }
-  if (getenv("KLF_DIAG")) {
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_run0).count();
-    fprintf(stderr, "[klf] run %.1f us: allocations %.1f us, first-batch tuning %.1f us\n", us,
-            (g_alloc_ns.load() - alloc0) / 1e3, tune_ns / 1e3);
-    std::string m = "[klf] run marks (us):";
-    auto prev = t_run0;
-    for (auto& x : marks) {
-      m += std::string(" ") + x.first + " " + std::to_string((int)std::chrono::duration<double, std::micro>(x.second - prev).count()) + ";";
-      prev = x.second;
-    }
-    fprintf(stderr, "%s\n", m.c_str());
-  }
-  if (overflow)  // the exact rerun overflowed too: never hand out the aborted run's records
+  if (p.k.diag) diag_summary(p);
+  if (next == kFail)  // never hand out the aborted run's records
     return set_err(e, KLF_ENOMEM, "line index / dense-tile pool overflow after the exact rerun");
-  if (const char* path = getenv("KLF_TIMELINE_OUT")) {  // diagnostic builds only
+  if (next == kRedo)  // every attempt asked for another
+    return set_err(e, KLF_ENOMEM, std::string("run not finished after 4 attempts (the last asked for a redo: ") +
+                                      kOutcomeName[o] + ")");
+  if (p.k.timeline_out) {  // diagnostic builds only
     std::vector<uint64_t> tl(300000 * 8);
     if (klf::dump_timeline(tl.data(), tl.size() * 8) == hipSuccess) {
-      if (FILE* f = fopen(path, "wb")) {
-        fwrite(tl.data(), 8, std::min<size_t>(tl.size(), ntiles * 8), f);
-        fclose(f);
-      }
+      FILE* fp = fopen(p.k.timeline_out, "wb");
+      if (fp) { fwrite(tl.data(), 8, std::min<size_t>(tl.size(), p.ntiles * 8), fp); fclose(fp); }
       (void)klf::clear_timeline();
     }
   }
-  // only the event pairs this run recorded (ev_mask): a pair it did not record would fail
-  // the query (or time an earlier run).  Timing is diagnostic: a recorded pair that fails to
-  // read leaves -1 in its slot (KLF_DIAG says so) and the filter result stands.
-  auto elapsed = [&](int k0, int k1, int slot) {
-    if (!((ev_mask >> k0 & 1u) && (ev_mask >> k1 & 1u))) return;
-    float ms = 0.f;
-    const hipError_t h = hipEventElapsedTime(&ms, e->ev[k0], e->ev[k1]);
-    if (h == hipSuccess) {
-      r->ms[slot] = ms;
-      return;
-    }
-    (void)hipGetLastError();  // (the failed query's error is not the next call's)
-    r->ms[slot] = -1.0;
-    if (getenv("KLF_DIAG"))
-      fprintf(stderr, "[klf] timing events %d/%d unreadable: %s\n", k0, k1, hipGetErrorString(h));
-  };
-  static const int kPairs[6][3] = {{1, 2, 0}, {2, 3, 1}, {3, 4, 2}, {4, 5, 3}, {0, 5, 4}, {0, 1, 5}};
-  const auto t_q0 = std::chrono::steady_clock::now();
-  for (const auto& q : kPairs) elapsed(q[0], q[1], q[2]);
-  elapsed(7, 8, 6);   // k_scan's dispatch alone
-  elapsed(9, 10, 7);  // k_tcopy's dispatch alone (dense copy)
-  if (diag_marks)
-    fprintf(stderr, "[klf] timing queries %.1f us\n",
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_q0).count());
-  r->ev_mask = ev_mask;
-  r->total_lines = r->so[nsegs - 1].line_hi;
-  for (auto& s : r->so) r->total_out = std::max(r->total_out, s.out_hi);
+  query_timing(p, r, at.ev_mask);
+  r->total_lines = r->so[p.nsegs - 1].line_hi;
+  for (auto& so : r->so) r->total_out = std::max(r->total_out, so.out_hi);
   *out = rp.release();
   return KLF_OK;
 }
@@ -1855,17 +1860,11 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
     }
     if (h == hipSuccess)
       h = klf::launch_retail(a, st, e->ev, e->num_cus, &rmask, regroup ? &g : nullptr, cut ? &wa : nullptr);
-    uint32_t short_out = 0;
+    uint32_t counters[32] = {0};
     if (h == hipSuccess) h = e->h_rb.ensure(kCtrBytes + nsegs * sizeof(SegOut));
-    if (h == hipSuccess)
-      h = hipMemcpyAsync(e->h_rb.p, e->d_counters.p, kCtrBytes + nsegs * sizeof(SegOut), hipMemcpyDeviceToHost, st);
-    if (h == hipSuccess) h = hipStreamSynchronize(st);
-    if (h == hipSuccess) {
-      memcpy(r->so.data(), e->h_rb.as<uint8_t>() + kCtrBytes, nsegs * sizeof(SegOut));
-      short_out = static_cast<uint32_t*>(e->h_rb.p)[klf::kCtrOutShort];
-      r->compaction = static_cast<uint32_t*>(e->h_rb.p)[klf::kCtrDense] ? KLF_COMPACT_TILES : KLF_COMPACT_GATHER;
-    }
-    if (h == hipSuccess && short_out) h = grow_out_retail(e, a, r->so);  // a larger window than the buffer holds
+    if (h == hipSuccess) h = read_back(e, nsegs, 0, 0, counters, r->so.data());
+    if (h == hipSuccess) r->compaction = counters[klf::kCtrDense] ? KLF_COMPACT_TILES : KLF_COMPACT_GATHER;
+    if (h == hipSuccess && counters[klf::kCtrOutShort]) h = grow_out_retail(e, a, r->so);  // a larger window than the buffer holds
     if (h == hipSuccess) e->last_args = a;
     if (h != hipSuccess) { delete r; return hip_err(e, h, what); }
     if ((rmask & 1u) && (rmask >> 5 & 1u)) {
