@@ -646,6 +646,8 @@ extern "C" int klf_open(const klf_config* cfg, klf_engine** out) {
   if (getenv("KLF_DIAG"))
     fprintf(stderr, "[klf] open: pattern compile %.1f us\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_open0).count());
+  if (getenv("KLF_DIAG") && compiled && e->cs.qf_on && !tune_later)  // (tuned: the first run prints it)
+    fprintf(stderr, "[klf] prefilter layout from 0 sampled bytes: %s\n", e->cs.qf_layout.c_str());
   if (!compiled) {
     // keep the engine alive so the caller can read klf_last_error; report failure
     e->err = err;

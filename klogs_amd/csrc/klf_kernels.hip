@@ -175,7 +175,6 @@ __device__ __forceinline__ uint16_t make_meta(bool ok, bool since_ok, uint32_t p
 constexpr uint32_t kSlotOff = 0x3FFFu, kSlotDefer = 0x4000u, kSlotHit = 0x8000u;
 constexpr uint32_t kCtrDefer = 5;  // counters[5]: some line of this run was deferred
 constexpr uint32_t kTsInline = 16u;  // TileStat.flags: the tile's single line slot is its pool_base word
-constexpr uint32_t kTsHitInline = 32u;  // TileStat.flags (general sets): its 1-2 prefilter hits are pool_base's halves
 // Kept runs of one tile (a selected line carries a >= 20-B prefix, so at most kTile / 20
 // + 2 runs: the carried-in line's and those of the lines starting in the tile) and its
 // 16-B output chunks (513 at most, in groups of 8: 16-B LDS accesses).
@@ -431,31 +430,13 @@ __device__ __forceinline__ bool parse_fast(const uint8_t* lds, uint32_t o, const
 // each, gpurun_out/r5d, r5e)
 #define KLF_SCAN_NT 1
 #endif
-#ifndef KLF_SCAN_PRIO
-#define KLF_SCAN_PRIO 0  // s_setprio level while a wave stages its tile and issues the next one
-#endif
-#ifndef KLF_NL_MASK
-#define KLF_NL_MASK 1  // the exact newline positions with the three-op test (eq_mask16_nl)
-#endif
-#ifndef KLF_SCAN_BALLOT
-#define KLF_SCAN_BALLOT 1  // per-lane 0/1 counts (sparse lines) summed / ranked by ballots
-#endif
-#ifndef KLF_SCAN_PACKSUM
-#define KLF_SCAN_PACKSUM 1  // the tile's parsed / since_ok counts in one wave reduction
-#endif
 #ifndef KLF_VERIFY_PAR
 #define KLF_VERIFY_PAR 0  // k_verify: 1 loads a needle's dwords 1..7 at once (C4: 468 vs 452 us, more VGPRs, r6e)
 #endif
-#ifndef KLF_HIT_INLINE
-#define KLF_HIT_INLINE 0  // 1: a tile's 1-2 prefilter hits in its TileStat (C4 k_scan +2.8 %, r6e)
-#endif
-#ifndef KLF_TS_INLINE
-#define KLF_TS_INLINE 1  // a tile where one line starts keeps its slot in the TileStat (no record store)
-#endif
-#ifndef KLF_SCAN_SUMSKIP
-// no count reductions on tiles where no line starts (C5: ~half its tiles): 6.33 -> 6.29 ms
-#define KLF_SCAN_SUMSKIP 1
-#endif
+// (Settled and no longer switchable, the variants in the history: a wave priority while a
+// tile is staged and a tile's one or two prefilter hits kept in its TileStat measured no
+// faster / 2.8 % slower on C4; the three-op newline mask, ballot ranks for sparse lines, the
+// packed parsed / since_ok reduction and the single line slot in the TileStat are the scan.)
 typedef uint32_t klf_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_nt(const uint4* p) {
   const klf_v4u v = __builtin_nontemporal_load(reinterpret_cast<const klf_v4u*>(p));
@@ -486,11 +467,293 @@ __device__ __forceinline__ uint4 ld_nt(const uint4* p) {
 // q-gram prefilter (QS = sampling stride).
 constexpr int kScanPlain = 0, kScanLit = 1, kScanGen = 2;
 
-// The tile descriptors come in as separate __restrict__ const parameters so that their
-// (wave-uniform) reads compile to scalar loads: a vector load of them would be ordered
-// behind the in-flight prefetch by vmcnt and stall every tile on the next tile's bytes.
-// General sets: QS sampling stride, QK bits per gram, QQ gram bytes (3 or 4), QA (stride 8
-// only) the short needles' anchor test (DevPatterns::qf_anc_*).
+// ---- k_scan's per-tile phases -------------------------------------------------------------
+// k_scan below reads top to bottom: set-up, then per tile  stage -> any_tests -> line_events
+// -> tile_starts -> line_work (list_lines, parse_lines, the one-pass compaction or the plan,
+// lit_grep) -> QProbe / anchored_hits -> emit_hits -> store_record.  Every phase is inlined
+// into the kernel; a phase takes the tile's context and the earlier phases' results by value
+// or const reference and hands its own back the same way (no pointers to registers).
+//
+// Timing builds (KLF_ABL != 0, scripts/variant.sh): the first launch is the full scan;
+// from the second launch on (a wave knows once every wave of an earlier launch has
+// finished) the ablated scan runs and stores nothing, so the first launch's records feed
+// the downstream kernels (identical batches) and no ablation can misdirect them.
+// KLF_ABL bits: 2 no literal anchor test, 64 staging + any-test only, 1 no timestamp
+// parse, 128 no line list / parse / literal, 4 no prefilter fast pass, 16 no second stage of
+// the two-level probe, 8 prefilter probes only, 65536 only the slot stores dropped, 131072
+// only the TileStat stores; 4096 = nothing removed (the scan without its stores).
+#define ABL(c, x) ((KLF_ABL & (x)) && (c).abl)
+
+// the scan's prefetch loads: non-temporal in the literal / general scans (not the plain one:
+// C3's k_tcopy re-reads the input, 5.15 -> 5.18 ms with them)
+template <int MODE>
+__device__ __forceinline__ uint4 ld_row(const uint4* p) {
+  return (KLF_SCAN_NT && MODE != kScanPlain) ? ld_nt(p) : *p;
+}
+// The tile in flight: eight 1 KiB rows (16 B per lane each) and the halo.  Named registers:
+// an array here was put on the scratch stack.
+#define KLF_ROWS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+struct TileRows {
+  static_assert(kTile / 1024 == 8, "KLF_ROWS lists the 8 prefetch rows");
+  uint4 r0, r1, r2, r3, r4, r5, r6, r7;
+  uint4 halo = make_uint4(0, 0, 0, 0);
+  template <int MODE>
+  __device__ __forceinline__ void load(const uint4* gp, int lane) {
+#define KLF_LOAD(k) r##k = ld_row<MODE>(&gp[k * 64 + lane]);
+    KLF_ROWS(KLF_LOAD)
+#undef KLF_LOAD
+    if (lane < kHalo / 16) halo = ld_row<MODE>(&gp[kTile / 16 + lane]);
+  }
+  __device__ __forceinline__ void store(uint8_t* s_tile, int lane) const {
+    uint4* l = reinterpret_cast<uint4*>(s_tile);
+#define KLF_STORE(k) l[k * 64 + lane] = r##k;
+    KLF_ROWS(KLF_STORE)
+#undef KLF_STORE
+    if (lane < kHalo / 16) l[kTile / 16 + lane] = halo;
+  }
+};
+#undef KLF_ROWS
+__device__ __forceinline__ const uint4* tile_bytes(const uint8_t* bytes, const SegDesc& sd, uint32_t tile) {
+  return reinterpret_cast<const uint4*>(bytes + sd.base + (uint64_t)(tile - sd.tile0) * kTile);
+}
+
+// One tile as its wave sees it: the wave-uniform part (stream, position in it) and the
+// lane's slice (kLaneBytes contiguous bytes from tile offset my0, nvalid of them in the stream).
+struct ScanTile {
+  uint32_t tile, s;
+  SegDesc sd;
+  int64_t rel_lo, seg_len;
+  int32_t tile_len;
+  bool first, last;  // the stream's first / last tile
+  const uint8_t* segp;
+  int lane;
+  uint32_t my0;
+  int nvalid;
+  bool abl;  // timing builds: an ablated launch (stores nothing)
+};
+__device__ __forceinline__ ScanTile scan_tile(const uint8_t* bytes, uint32_t tile, uint32_t s, const SegDesc& sd,
+                                              int lane, bool abl) {
+  ScanTile c;
+  c.tile = tile;
+  c.s = s;
+  c.sd = sd;
+  c.rel_lo = (int64_t)(tile - sd.tile0) * kTile;
+  c.seg_len = (int64_t)sd.len;
+  c.tile_len = (int32_t)(c.seg_len - c.rel_lo < kTile ? c.seg_len - c.rel_lo : kTile);
+  c.first = c.rel_lo == 0;
+  c.last = c.rel_lo + kTile >= c.seg_len;
+  c.segp = bytes + sd.base;
+  c.lane = lane;
+  c.my0 = (uint32_t)lane * kLaneBytes;
+  const int nvalid_s = c.tile_len - (int)c.my0;
+  c.nvalid = nvalid_s <= 0 ? 0 : (nvalid_s >= kLaneBytes ? kLaneBytes : nvalid_s);
+  c.abl = abl;
+  return c;
+}
+// a 16-bit mask of chunk ch of the lane's bytes without the bytes past the tile's end
+__device__ __forceinline__ uint32_t clip_chunk(const ScanTile& c, uint32_t e, uint32_t ch) {
+  const int nv = c.nvalid - 16 * (int)ch;
+  return nv >= 16 ? e : (nv <= 0 ? 0u : (e & ((1u << nv) - 1u)));
+}
+__device__ __forceinline__ uint4 lane_chunk(const uint8_t* s_tile, const ScanTile& c, uint32_t ch) {
+  return *reinterpret_cast<const uint4*>(s_tile + c.my0 + 16u * ch);
+}
+__device__ __forceinline__ uint4 or4(const uint4& x, uint32_t f) { return make_uint4(x.x | f, x.y | f, x.z | f, x.w | f); }
+// v[q] |= x for a q in 0..3 known only at run time (selects, no indexed registers)
+__device__ __forceinline__ void or_quad(uint32_t (&v)[4], uint32_t q, uint32_t x) {
+  v[0] |= q == 0 ? x : 0u;
+  v[1] |= q == 1 ? x : 0u;
+  v[2] |= q == 2 ? x : 0u;
+  v[3] |= q == 3 ? x : 0u;
+}
+
+// ---- any-tests over my 128 bytes: 8 chunks of 16 B, read rotated (chunk (v + lane/2)
+// mod 8) so that every 16-lane group of a ds_read_b128 covers all 64 banks once.  Bit c of
+// nlc / anc: chunk c may hold a '\n' / the anchor byte (pat: the fused literal's rarest
+// byte, or the short needles' anchor -- loose short needles: bytes tested OR afold).
+struct AnyHits {
+  uint32_t nlc, anc;
+};
+template <bool LIT, bool ANC>
+__device__ __forceinline__ AnyHits any_tests(const uint8_t* s_tile, const ScanTile& c, uint32_t pat, uint32_t afold) {
+  uint32_t nlc = 0, anc = 0;
+  const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
+  // KLF_ANY_BATCH reads in flight before the first test (8: one LDS round trip, not
+  // eight; 4: two round trips, 16 fewer VGPRs)
+#pragma unroll
+  for (int v0 = 0; v0 < 8; v0 += KLF_ANY_BATCH) {
+    uint4 xs[KLF_ANY_BATCH];
+#pragma unroll
+    for (int v = 0; v < KLF_ANY_BATCH; ++v) xs[v] = lane_chunk(s_tile, c, ((uint32_t)(v0 + v) + rot) & 7u);
+#pragma unroll
+    for (int v = 0; v < KLF_ANY_BATCH; ++v) {
+      const uint32_t ch = ((uint32_t)(v0 + v) + rot) & 7u;
+      nlc |= any_eq16(xs[v], 0x0A0A0A0Au) ? (1u << ch) : 0u;
+      if (LIT && !ABL(c, 2)) anc |= any_eq16(xs[v], pat) ? (1u << ch) : 0u;
+      if (ANC) anc |= any_eq16(afold ? or4(xs[v], afold) : xs[v], pat) ? (1u << ch) : 0u;
+    }
+  }
+  if (c.nvalid < kLaneBytes) {
+    const uint32_t vm = (1u << ((c.nvalid + 15) >> 4)) - 1u;
+    nlc &= vm;
+    anc &= vm;
+  }
+  return AnyHits{nlc, anc};
+}
+
+// ---- exact line-end positions in the chunks that hit: a 128-bit event mask (em), the
+// events that start a line (st: the stream's end is an event too -- it closes the last line
+// -- and starts none), my event count and its inclusive scan over the wave, the tile's total.
+// The lane holding the stream's last byte stores the stream's frag (no final '\n').
+struct LineEvents {
+  uint32_t em[4], st[4];
+  uint32_t cnt, incl, agg;
+};
+__device__ __forceinline__ LineEvents line_events(const uint8_t* s_tile, const ScanTile& c, uint32_t nlc, SegOut* segout) {
+  LineEvents ev;
+  ev.em[0] = ev.em[1] = ev.em[2] = ev.em[3] = 0u;
+  for (uint32_t m = nlc; m; m &= m - 1u) {
+    const uint32_t ch = (uint32_t)__builtin_ctz(m);
+    or_quad(ev.em, ch >> 1, clip_chunk(c, eq_mask16_nl(lane_chunk(s_tile, c, ch)), ch) << ((ch & 1u) * 16u));
+  }
+  ev.st[0] = ev.em[0]; ev.st[1] = ev.em[1]; ev.st[2] = ev.em[2]; ev.st[3] = ev.em[3];
+  if (c.last && c.nvalid > 0 && (int)c.my0 + c.nvalid == c.tile_len) {
+    const uint32_t eb = (uint32_t)c.nvalid - 1u, q = eb >> 5, bit = 1u << (eb & 31u);
+    bool nl_at_end = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((uint32_t)k == q) {
+        nl_at_end = (ev.em[k] & bit) != 0u;
+        ev.em[k] |= bit;
+        ev.st[k] &= ~bit;
+      }
+    if (!c.abl) segout[c.s].frag = nl_at_end ? 0 : 1;
+  }
+  ev.cnt = (uint32_t)(__popc(ev.em[0]) + __popc(ev.em[1]) + __popc(ev.em[2]) + __popc(ev.em[3]));
+  // (at most one event per lane -- lines of 128 B and more: a ballot's rank is the scan)
+  ev.incl = !__any(ev.cnt > 1u)
+                ? ev.cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(__ballot(ev.cnt != 0u) >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)__ballot(ev.cnt != 0u), 0u))
+                : wave_incl_scan_add(ev.cnt, c.lane);
+  ev.agg = (uint32_t)__builtin_amdgcn_readlane((int)ev.incl, 63);
+  return ev;
+}
+
+// ---- the lines starting in the tile.  Local line k = the line after the tile's k-th event
+// (k = 0: the line open at the tile start); lines starting here: k in [k0, k0 + nlines),
+// slot j = k - k0.  A dense tile (more starts than kSlots) takes its slots from the pool.
+struct TileStarts {
+  uint32_t k0, nlines, pool_base;
+  bool dense, pool_ok;
+};
+__device__ __forceinline__ TileStarts tile_starts(const RunArgs& a, const ScanTile& c, uint32_t agg) {
+  TileStarts tl;
+  tl.k0 = c.first ? 0 : 1;
+  const uint32_t k1 = c.last ? agg : agg + 1;
+  tl.nlines = k1 > tl.k0 ? k1 - tl.k0 : 0;
+  tl.dense = tl.nlines > (uint32_t)kSlots;
+  tl.pool_base = 0;
+  if (tl.dense) {
+    uint32_t pb = 0;
+    if (c.lane == 0 && !c.abl) {
+      pb = atomicAdd(&a.counters[kCtrPool], (tl.nlines + 31u) & ~31u);  // (whole 128-B lines: the waves' chunks stay aligned)
+      if ((uint64_t)pb + tl.nlines > a.pool_cap) atomicOr(a.counters + 2, 1u);
+    }
+    tl.pool_base = (uint32_t)__builtin_amdgcn_readlane((int)pb, 0);
+  }
+  tl.pool_ok = !tl.dense || (uint64_t)tl.pool_base + tl.nlines <= a.pool_cap;
+  return tl;
+}
+
+// what one lane counted over the tile's lines (summed / reduced over the wave by their readers)
+struct LineCounts {
+  uint32_t parsed = 0, since = 0, defer = 0, carry = 0, hits = 0;
+};
+
+// ---- line starts -> list[j] = start offset in the tile (the LDS list, or a dense tile's
+// pool slots) ----
+__device__ __forceinline__ void list_lines(uint32_t* list, const ScanTile& c, const LineEvents& ev, const TileStarts& tl) {
+  if (c.first && c.lane == 0) list[0] = 0u;
+  uint32_t kk = ev.incl - ev.cnt;  // events before my bytes
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    for (uint32_t e = ev.em[q]; e; e &= e - 1u) {
+      const uint32_t b = (uint32_t)__builtin_ctz(e);
+      ++kk;
+      if ((ev.st[q] >> b) & 1u) list[kk - tl.k0] = c.my0 + 32u * q + b + 1u;
+    }
+  }
+  if (tl.dense) __threadfence_block();
+  wave_lds_sync();
+}
+// ---- timestamp + since: one line per lane; list[j] gains its meta or its defer bit ----
+template <bool FUSE>
+__device__ __forceinline__ void parse_lines(uint32_t* list, const uint8_t* s_tile, const RunArgs& a, const ScanTile& c,
+                                            uint32_t nlines, LineCounts& n) {
+  for (uint32_t b0 = 0; b0 < nlines; b0 += 64) {
+    const uint32_t j = b0 + (uint32_t)c.lane;
+    if (j >= nlines) continue;
+    const uint32_t off = list[j];
+    bool so = false, fast = false;
+    if (ABL(c, 1)) {
+      fast = so = true;
+    } else if (c.rel_lo + (int64_t)off + 31 <= c.seg_len) {
+      fast = parse_fast(s_tile, off, a.since_dig, so);
+    }
+    if (FUSE && !fast) {  // the one-pass compaction decides every line here: Go time.Parse
+      TsResult tr;
+      uint32_t plen = 0;
+      const bool ok = parse_line_prefix(GlobalBytes{c.segp, c.rel_lo + (int64_t)off, c.seg_len}, tr, plen);
+      const bool so2 = ok && !time_before(tr.sec, tr.nsec, a.since_sec, a.since_nsec);
+      list[j] = off | ((uint32_t)make_meta(ok, so2, ok ? plen : 0u) << 16);
+      if (ok && plen >= kPlenEscape) atomicOr(&a.counters[kCtrFuseBad], 1u);  // (a prefix longer than the meta holds)
+      n.parsed += ok ? 1u : 0u;
+      n.since += so2 ? 1u : 0u;
+    } else {
+      list[j] = fast ? (off | ((uint32_t)make_meta(true, so, 31) << 16)) : (off | kSlotDefer);
+      n.parsed += fast ? 1u : 0u;
+      n.since += (fast && so) ? 1u : 0u;
+      n.defer += fast ? 0u : 1u;
+    }
+  }
+}
+
+// ---- kept runs: one round of 64 list entries -> this lane's run (tile offset and length of
+// a selected line's content inside the tile), its offset among the tile's kept bytes and its
+// index among the runs (both scanned over the rounds so far); the one-pass compaction and the
+// planned runs differ only in where the run word goes.
+struct KeptRuns {  // over a tile's rounds: runs, kept bytes, selected lines counted in this stream;
+  uint32_t nr = 0, bytes = 0, nsel = 0, lsel = 0;  // (per lane) my line's kept bit and content
+  int32_t lcrel = -1;                              // start - the tile end, read at the last line's lane
+};
+struct KeptRun {
+  uint32_t src, len, dst, idx;
+};
+__device__ __forceinline__ KeptRun kept_runs_round(const uint32_t* list, uint32_t b0, uint32_t nlines, int32_t tile_len,
+                                                   int lane, KeptRuns& k) {
+  const uint32_t j = b0 + (uint32_t)lane;
+  uint32_t src = 0, len = 0;
+  bool sel = false, starts = false;
+  if (j < nlines) {
+    const uint32_t v = list[j], off = v & kSlotOff, mt = v >> 16;
+    sel = !(v & kSlotDefer) && (mt & Meta::kParsed) && (mt & Meta::kSince);
+    const uint32_t cs = off + (mt >> 2);
+    const uint32_t e = j + 1 < nlines ? (list[j + 1] & kSlotOff) : (uint32_t)tile_len;
+    if (sel && e > cs) { src = cs; len = e - cs; }
+    // (a line starting at the tile end -- the last byte is '\n' -- starts the next
+    // tile, whose list does not hold it: counted here, in its stream)
+    starts = off <= (uint32_t)tile_len;
+    if (j + 1 == nlines) { k.lsel = sel ? 1u : 0u; k.lcrel = f_sat((int32_t)cs - tile_len); }
+  }
+  const uint32_t incl = wave_incl_scan_add(len, lane);
+  const uint64_t bm = __ballot(len != 0);
+  const KeptRun r{src, len, k.bytes + incl - len, k.nr + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull))};
+  k.nr += (uint32_t)__popcll(bm);
+  k.bytes += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  k.nsel += (uint32_t)__popcll(__ballot(sel && starts));
+  return r;
+}
+
 __device__ __forceinline__ void copy_tile_runs(const uint8_t* s_buf, uint32_t* s_run, uint16_t* s_map, uint32_t nr,
                                                uint32_t kept, uint64_t obase, uint8_t* out, int lane);
 
@@ -504,6 +767,590 @@ __device__ __forceinline__ void copy_tile_runs(const uint8_t* s_buf, uint32_t* s
 // from the state the earlier ranges left (fuse_rinfo) once every range has been scanned.
 // A dense tile or a deferred line voids the pass (counters[kCtrFuseBad]: the host reruns
 // the two-pass compaction).
+// The state of the wave's range (wave-uniform): whether the line open at the current tile
+// start is decided (a line started in this range's part of the stream, or the part began
+// at the stream's start), that line's kept bit and content start - the tile start (f_sat),
+// the output position, the current extent.
+struct FuseState {
+  bool known = false, sel = false, res_set = false;
+  int32_t crel = -1;
+  uint64_t obase = 0, estart = 0, res = 0, part = 0, rbase = 0;
+  uint32_t ext = 0;
+  // closes the current extent (a range part that saw no line start: all of it is left to
+  // k_fcarry, the extent empty at its end)
+  __device__ __forceinline__ void close(uint64_t* fuse_ext, int lane) {
+    if (!res_set) {
+      res = part;
+      res_set = true;
+      estart = obase = rbase + part;
+    }
+    if (lane == 0) {
+      fuse_ext[2 * (size_t)ext] = estart;
+      fuse_ext[2 * (size_t)ext + 1] = obase - estart;
+    }
+  }
+  // one (not dense) tile: its kept runs -- the carried-in line's, then the lines starting
+  // here -- copied to the range's output at once
+  __device__ __forceinline__ void advance(const RunArgs& a, const ScanTile& c, const uint32_t* list, uint32_t nlines,
+                                          bool tile_defers, bool range_start, const uint8_t* s_tile, uint32_t* s_frun,
+                                          uint16_t* s_fmap) {
+    if (tile_defers && c.lane == 0) a.counters[kCtrFuseBad] = 1u;  // decided later: rerun
+    const uint64_t tin = c.sd.base + (uint64_t)c.rel_lo;  // the tile's input = output position
+    if (c.first) {  // a stream starts here: nothing carried in
+      if (!range_start) {
+        close(a.fuse_ext, c.lane);
+        ++ext;
+      } else {
+        res_set = true;
+      }
+      known = true;
+      sel = false;
+      crel = -1;
+      obase = estart = tin;
+      part = 0;
+    }
+    const uint32_t span = nlines ? (list[0] & kSlotOff) : (uint32_t)c.tile_len;
+    uint32_t clen = 0, csrc = 0;
+    if (known) {
+      clen = f_carried(span, sel, crel);
+      csrc = crel > 0 ? (uint32_t)crel : 0u;
+    } else if (nlines) {  // the range's first line start: the bytes before it are k_fcarry's
+      res = part + span;
+      res_set = true;
+      obase = estart = tin + span;
+    }
+    KeptRuns k;
+    for (uint32_t b0 = 0; b0 < nlines; b0 += 64) {
+      const KeptRun r = kept_runs_round(list, b0, nlines, c.tile_len, c.lane, k);
+      if (r.len) s_frun[1 + r.idx] = r.src | ((clen + r.dst) << 16);
+    }
+    if (clen && c.lane == 0) s_frun[0] = csrc;  // (output offset 0)
+    const uint32_t kept = clen + k.bytes;
+    if (kept) {
+      if (obase + kept + 16 > a.out_cap) {
+        if (c.lane == 0) a.counters[kCtrFuseBad] = 1u;
+      } else {
+        copy_tile_runs(s_tile, clen ? s_frun : s_frun + 1, s_fmap, k.nr + (clen ? 1u : 0u), kept, obase, a.out, c.lane);
+      }
+      obase += kept;
+    }
+    if (nlines) {
+      const uint32_t lastl = (nlines - 1u) & 63u;
+      sel = __builtin_amdgcn_readlane((int)k.lsel, (int)lastl) != 0;
+      crel = __builtin_amdgcn_readlane(k.lcrel, (int)lastl);
+      known = true;
+    } else if (known) {
+      crel = f_sat(crel - c.tile_len);
+    }
+    part += (uint64_t)c.tile_len;
+  }
+  // the range's last extent and the state it leaves (fuse_rinfo)
+  __device__ __forceinline__ void finish(const RunArgs& a, uint32_t range, int lane) {
+    close(a.fuse_ext, lane);
+    if (lane == 0) {
+      uint64_t* ri = a.fuse_rinfo + 4 * (size_t)range;
+      ri[0] = res;
+      ri[1] = (known ? 1u : 0u) | (sel ? 2u : 0u);
+      ri[2] = (uint64_t)(int64_t)crel;
+      ri[3] = part;
+    }
+  }
+};
+
+// ---- planned dense compaction: the tile's own kept runs and aggregate (FAgg above).
+// Two rounds of 64 lines, each ending in one buffer store of the runs (lanes without a
+// run, or past the record, dropped) and the plan in one more.  The store count per tile is
+// fixed -- the second run store issues whether or not nlines > 64 -- see store_record.
+// Tiles with more lines leave their runs to k_tcopy (kRunsRecompute).
+__device__ __forceinline__ void plan_tile(const RunArgs& a, const ScanTile& c, const uint32_t* list, uint32_t nlines) {
+  typedef uint32_t u32x4p __attribute__((ext_vector_type(4)));
+  const bool fits = nlines <= 128u && !c.abl;
+  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+      a.truns + (size_t)c.tile * kRunSlots, 0, fits ? kRunSlots * 4 : 0, 0x00020000);
+  KeptRuns k;
+  // a round's run word and its store offset (slot 0 is the carried-in run's, k_cmove; no run: dropped)
+  auto word = [](const KeptRun& r) { return r.src | (r.dst << 16); };
+  auto offs = [](const KeptRun& r) { return r.len ? 4u * (r.idx + 1u) : 0x7FFF0000u; };
+  const KeptRun r0 = kept_runs_round(list, 0u, nlines, c.tile_len, c.lane, k);
+  __builtin_amdgcn_raw_buffer_store_b32(word(r0), rr, offs(r0), 0, 0);
+  KeptRun r1{0u, 0u, 0u, 0u};
+  if (nlines > 64u) r1 = kept_runs_round(list, 64u, nlines, c.tile_len, c.lane, k);
+  __builtin_amdgcn_raw_buffer_store_b32(word(r1), rr, offs(r1), 0, 0);
+  for (uint32_t b0 = 128u; b0 < nlines; b0 += 64) kept_runs_round(list, b0, nlines, c.tile_len, c.lane, k);  // (no runs stored)
+  const uint32_t lastl = nlines ? ((nlines - 1u) & 63u) : 0u;
+  const uint32_t psel = nlines ? (uint32_t)__builtin_amdgcn_readlane((int)k.lsel, (int)lastl) : 0u;
+  const int32_t pcrel = nlines ? __builtin_amdgcn_readlane(k.lcrel, (int)lastl) : -1;
+  const uint32_t span = nlines ? (list[0] & kSlotOff) : (uint32_t)c.tile_len;
+  const uint32_t px = (k.bytes & 0x3FFFu) | ((span & 0x3FFFu) << 14) | ((nlines ? 1u : 0u) << 28) | (psel << 29);
+  const uint32_t py = ((uint32_t)(uint16_t)(int16_t)pcrel) | (k.nsel << 16);
+  const uint32_t pz = (fits && k.nr + 1u <= (uint32_t)kRunSlots) ? k.nr : (uint32_t)kRunsRecompute;
+  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(a.trec + c.tile, 0, c.abl ? 0 : 16, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(u32x4p{px, py, pz, kPlanTag}, pr, c.lane ? 0x7FFF0000u : 0u, 0, 0);
+}
+
+// ---- fused single-literal grep ----
+// number of listed line starts at or before tile offset pos
+__device__ __forceinline__ int starts_upto(const uint32_t* list, uint32_t nlines, int32_t pos) {
+  int lo = 0, hi = pos < 0 ? 0 : (int)nlines;  // pos < 0: in the carried-in line
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((list[mid] & kSlotOff) <= (uint32_t)pos) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// a final (literal) hit starting at tile offset pos -> its line's hit bit
+__device__ __forceinline__ void attribute(uint32_t* list, uint32_t nlines, int32_t pos, LineCounts& n) {
+  const int lo = starts_upto(list, nlines, pos);
+  if (lo > 0) {  // the line starts in this tile: deferred lines are searched by k_fixup
+    const uint32_t v = list[lo - 1];
+    const uint32_t mt = v >> 16;
+    if (!(v & kSlotDefer) && (mt & Meta::kParsed) && (uint32_t)pos >= (v & kSlotOff) + (mt >> 2)) {
+      atomicOr(&list[lo - 1], kSlotHit);
+      ++n.hits;
+    }
+  } else {  // carried in from an earlier tile: k_scatter decides (furthest hit wins)
+    const uint32_t c1 = (uint32_t)(pos + 1 + (int32_t)kCarryBias);  // pos >= -kCarryBias
+    n.carry = n.carry > c1 ? n.carry : c1;
+  }
+}
+// the literal (m bytes, s_lit) at tile offset pos?  Then the hit is attributed
+__device__ __forceinline__ void lit_check(uint32_t* list, uint32_t nlines, const uint8_t* s_tile, const uint32_t* s_lit,
+                                          const ScanTile& c, uint32_t m, int32_t pos, LineCounts& n) {
+  if (pos < 0 || pos >= c.tile_len || c.rel_lo + pos + (int64_t)m > c.seg_len) return;
+  bool eq = true;
+  if ((uint32_t)pos + m + 4 <= (uint32_t)(kTile + kHalo)) {  // 4 bytes per LDS read
+    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
+    const uint32_t sh = (uint32_t)pos & 3u;
+    uint32_t wi = (uint32_t)pos >> 2;
+    uint32_t prev = s32[wi];
+    for (uint32_t k = 0; k < m && eq; k += 4) {
+      const uint32_t nx = s32[++wi];
+      const uint32_t got = __builtin_amdgcn_alignbyte(nx, prev, sh);
+      prev = nx;
+      const uint32_t nb = m - k < 4 ? m - k : 4;
+      const uint32_t msk = nb == 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1);
+      eq = ((got ^ s_lit[k >> 2]) & msk) == 0;
+    }
+  } else {
+    const uint8_t* lit = reinterpret_cast<const uint8_t*>(s_lit);
+    for (uint32_t k = 0; k < m && eq; ++k) {
+      const uint32_t o = (uint32_t)pos + k;
+      const uint8_t b = o < (uint32_t)(kTile + kHalo) ? s_tile[o] : c.segp[c.rel_lo + o];
+      eq = b == lit[k];
+    }
+  }
+  if (eq) attribute(list, nlines, pos, n);
+}
+// Anchor hits (the literal's rarest byte) name candidate starts p = anchor - ka.  A
+// tile owns the starts inside it: anchors whose start lies in the previous tile are
+// left to that tile, which scans its halo.
+__device__ __forceinline__ void lit_grep(uint32_t* list, uint32_t nlines, const uint8_t* s_tile, const uint32_t* s_lit,
+                                         const RunArgs& a, const ScanTile& c, uint32_t anc, uint32_t pat, LineCounts& n) {
+  const uint32_t m = a.lit_len, ka = a.lit_anchor;
+  for (uint32_t cm = anc; cm; cm &= cm - 1u) {
+    const uint32_t ch = (uint32_t)__builtin_ctz(cm);
+    for (uint32_t e = clip_chunk(c, eq_mask16(lane_chunk(s_tile, c, ch), pat), ch); e; e &= e - 1u)
+      lit_check(list, nlines, s_tile, s_lit, c, m, (int32_t)(c.my0 + 16u * ch + (uint32_t)__builtin_ctz(e)) - (int32_t)ka, n);
+  }
+  if (c.lane == 63 && ka > 0 && !c.last) {  // halo anchors -> starts in this tile's tail
+    for (uint32_t jj = 0; jj < ka; ++jj) {
+      const int64_t q = c.rel_lo + kTile + jj;
+      if (q >= c.seg_len) break;
+      const uint8_t b = jj < (uint32_t)kHalo ? s_tile[kTile + jj] : c.segp[q];
+      if (b == a.lit_anchor_byte) lit_check(list, nlines, s_tile, s_lit, c, m, (int32_t)(kTile + jj) - (int32_t)ka, n);
+    }
+  }
+  n.carry = wave_max(n.carry);
+}
+
+// ---- the per-tile work on the line list, instantiated for the LDS list (normal tiles) and
+// the global pool (dense tiles): list, parse, the one-pass compaction or the plan, the literal
+template <int MODE, bool FUSE>
+__device__ __forceinline__ void line_work(uint32_t* list, const RunArgs& a, const ScanTile& c, const LineEvents& ev,
+                                          const TileStarts& tl, const uint8_t* s_tile, const uint32_t* s_lit, uint32_t anc,
+                                          uint32_t pat, FuseState& fz, bool range_start, uint32_t* s_frun, uint16_t* s_fmap,
+                                          LineCounts& n) {
+  list_lines(list, c, ev, tl);
+  parse_lines<FUSE>(list, s_tile, a, c, tl.nlines, n);
+  if constexpr (MODE == kScanPlain && FUSE) {
+    if (!tl.dense) {  // (a dense tile voids the pass)
+      wave_lds_sync();
+      fz.advance(a, c, list, tl.nlines, __any(n.defer != 0), range_start, s_tile, s_frun, s_fmap);
+    }
+  } else if constexpr (MODE == kScanPlain) {
+    if (a.plan_runs) {
+      if (tl.dense) __threadfence_block();
+      wave_lds_sync();
+      plan_tile(a, c, list, tl.nlines);
+    }
+  }
+  if (MODE == kScanLit) {
+    if (tl.dense) __threadfence_block();
+    wave_lds_sync();
+    lit_grep(list, tl.nlines, s_tile, s_lit, a, c, anc, pat, n);
+  }
+  if (tl.dense) __threadfence_block();
+  wave_lds_sync();
+}
+
+// ---- general sets: fused q-gram prefilter ----
+// Samples p = 0 mod QS of the tile (each needle's chosen window is q + QS - 1 long, so
+// every occurrence spans exactly one sample whose gram lies in the window) probe the
+// LDS bitmap (one word, two bits per gram).  The few bitmap hits are appended to a global list
+// (one atomic per wave and tile) and verified by k_verify once the line index exists:
+// the scan keeps no verification code, and the latency-bound bucket walks run with
+// the whole GPU's parallelism.
+// A lane's hits: hq[q] bit b = the sample at tile offset my0 + 32 q + b; xh = one more hit's
+// tile offset (the two-level probe's compacted stage 2), none = kNoHit.
+constexpr uint32_t kNoHit = 0xFFFFFFFFu;
+template <int QS, int QK, int QQ>
+struct QProbe {
+  static constexpr bool kMidIdx = QQ == 3 && QK == 2;  // word from h bits 18..29 (qf_bucket)
+  static constexpr bool K3 = QK == 3 || QK == (int)kQfTwoLevel;  // three bits per gram
+  static constexpr bool TWO = QK == (int)kQfTwoLevel;            // pair stage first (stride 4 only)
+  static_assert(!TWO || QS == 4, "the two-level probe runs at stride 4");
+  static_assert(QQ == 3 || QQ == 4, "3- or 4-byte grams");
+  const uint32_t* s_qf;   // the needles' q-gram bitmap (LDS)
+  const uint8_t* s_tile;  // the staged tile (LDS)
+  uint32_t fold;
+  // bit 0 of test(): gram g has all K bits of its bitmap word set (qf_f / qf_hash /
+  // qf_bits): the multiplies, the word read, and the bit positions as byte / word selects
+  // or low bits of the products (SDWA operands of the shifts)
+  struct Hash {
+    uint32_t h, p, m, a;  // a: byte offset of the bitmap word in LDS (qf_bucket * 4)
+  };
+  // (the 24-bit multiplies ignore bits 24..31 of f: no mask)
+  __device__ __forceinline__ Hash hash(uint32_t g) const {
+    const uint32_t gf = g | fold;
+    const uint32_t f = K3 ? gf ^ bfe_u32(gf, 13, 11) : gf;
+    Hash r;
+    r.h = mul_u24(f, 0x9E3779u);
+    if (QQ == 4) r.h = mad_u24(gf >> 8, 0x7F4A7Du, r.h);  // + bytes 1..3 * C2
+    r.p = K3 ? mul_hi_u24(f, 0xC2B2AEu) : 0u;  // K = 2: both bits from h (qf_bits)
+    r.m = K3 ? mul_u24(f, 0x5BD1E9u) : 0u;
+    r.a = TWO ? (((r.h >> 21) << 2) + kQfPairWords * 4u)  // the Bloom half, 11-bit word
+          : kMidIdx ? ((r.h >> 16) & ((kQfWords - 1u) << 2)) : ((r.h >> (32 - kQfBucketBits)) << 2);
+    return r;
+  }
+  __device__ __forceinline__ uint32_t word(const Hash& r) const {
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_qf) + r.a);
+  }
+  __device__ __forceinline__ static uint32_t test(uint32_t w, const Hash& r) {
+    uint32_t t = K3 ? (w >> ((r.m >> 24) & 31u)) & (w >> (r.p & 31u))
+                    : shr_byte1(w, r.h) & (w >> ((r.h >> 16) & 31u));
+    if (K3) t &= w >> ((r.h >> 16) & 31u);
+    if (TWO) t &= shr_byte1(w, r.m);  // the fourth bit: m bits 8..12 (qf_bits)
+    return t;
+  }
+  __device__ __forceinline__ uint32_t hbits(uint32_t g) const {
+    const Hash r = hash(g);
+    return test(word(r), r);
+  }
+  // the samples of chunk ch (16 B) -> their grams, in order (QS = 8: dwords 0 and 2;
+  // QS = 6: the grid's bytes 0, 6 and 12, qf_sampled)
+  template <class F>
+  __device__ __forceinline__ void chunk_grams(const ScanTile& c, uint32_t ch, F&& f) const {
+    const uint32_t o0 = c.my0 + 16u * ch;
+    const uint4 x = *reinterpret_cast<const uint4*>(s_tile + o0);
+    if constexpr (QS == 6) {
+      f(x.x, 0);
+      f(__builtin_amdgcn_alignbyte(x.z, x.y, 2u), 6);
+      f(x.w, 12);
+      return;
+    }
+    const uint32_t w4 = QS < 4 ? reinterpret_cast<const uint32_t*>(s_tile)[(o0 >> 2) + 4] : 0u;
+    const uint32_t w[5] = {x.x, x.y, x.z, x.w, w4};
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int o = 0; o < 4; o += (QS < 4 ? QS : 4)) {
+        if ((4 * d + o) % QS != 0) continue;
+        f(o == 0 ? w[d] : __builtin_amdgcn_alignbyte(w[d + 1], w[d], o), 4 * d + o);
+      }
+  }
+  // Two-level probe, both stages: the hits go to hq, or (compacted stage 2) to xh.
+  // stage 1: the exact set of the probed grams' low two bytes (pair words [0, 2048)):
+  // sv bit i = the sample at my0 + 4i passes (each chunk's four dwords, two chunks per
+  // step with their eight word reads in flight).  The raw bytes probe: for a folded set
+  // the host lists every case variant of a pair (p with p | 0x2020 in the set), so the
+  // stage has no fold OR and the word's bit is the sample's own low five bits.  Step v
+  // puts chunk (v + rot) & 7 at bits 4v.. (constant shifts); one rotate at the end
+  __device__ __forceinline__ uint32_t pair_stage(const ScanTile& c) const {
+    const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
+    uint32_t sv = 0;
+#pragma unroll
+    for (int v = 0; v < (ABL(c, 4) ? 0 : 8); v += 2) {
+      const uint4 xa = lane_chunk(s_tile, c, ((uint32_t)v + rot) & 7u);
+      const uint4 xb = lane_chunk(s_tile, c, ((uint32_t)v + 1u + rot) & 7u);
+      const uint32_t g[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+      uint32_t w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        w[k] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_qf) + (bfe_u32(g[k], 5, 11) << 2));
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        sv |= __builtin_amdgcn_ubfe(w[k], g[k], 1u) << (4 * v + k);  // bit g mod 32 (v_bfe_u32 reads offset[4:0])
+    }
+    sv = __builtin_amdgcn_alignbit(sv, sv, 32u - 4u * rot);  // rotate left by 4 rot (shift mod 32): chunk c at bits 4c..
+    // samples at or past the tile's end (4i >= nvalid) do not count
+    return sv & (c.nvalid >= kLaneBytes ? ~0u : ((1u << ((uint32_t)(c.nvalid + 3) >> 2)) - 1u));
+  }
+  // stage 2: the survivors' 3-bit probe into the Bloom half.  The ~1.4 % survivors
+  // (~30 per tile) are compacted over the wave first, so that one round of 64 lanes
+  // probes them all (each lane's own walk took as many dependent LDS round trips as
+  // the busiest lane had survivors); a hit's tile offset goes to xh.  Past 64
+  // survivors each lane walks its own: a hit's byte position 4i -> its 32-B group
+  // q = i / 8, bit 4i mod 32.
+  // The survivor list reuses the last 32 words of the wave's slot list, free unless more
+  // than kSlotStride - 32 lines start in the tile (a 512-B LDS array of its own cost a third
+  // of the workgroups: 7.7 -> 10.4 ms)
+  __device__ __forceinline__ void two_level(const ScanTile& c, uint32_t* s_list, uint32_t nlines, uint32_t (&hq)[4],
+                                            uint32_t& xh) const {
+    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
+    uint32_t sv = pair_stage(c);
+    if (ABL(c, 16)) sv = 0u;  // (KLF_ABL 16: no stage 2)
+    const uint32_t scnt = (uint32_t)__popc(sv);
+    const uint32_t sincl = wave_incl_scan_add(scnt, c.lane);
+    const uint32_t stot = (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
+    if (stot <= 64u && nlines <= (uint32_t)kSlotStride - 32u) {
+      if (stot) {
+        uint16_t* sl = reinterpret_cast<uint16_t*>(s_list + kSlotStride - 32);
+        uint32_t k = sincl - scnt;
+        for (uint32_t m = sv; m; m &= m - 1u) sl[k++] = (uint16_t)(((uint32_t)c.lane << 5) | (uint32_t)__builtin_ctz(m));
+        wave_lds_sync();
+        if ((uint32_t)c.lane < stot) {
+          const uint32_t e = sl[c.lane];  // sample e & 31 of lane e >> 5: tile offset 4 e
+          if (hbits(s32[e]) & 1u) xh = 4u * e;
+        }
+        wave_lds_sync();  // (the next tile rewrites the list)
+      }
+    } else {
+      for (uint32_t m = sv; m; m &= m - 1u) {
+        const uint32_t i = (uint32_t)__builtin_ctz(m);
+        if (hbits(s32[(c.my0 >> 2) + i]) & 1u) or_quad(hq, i >> 3, 1u << ((4u * i) & 31u));
+      }
+    }
+  }
+  // Fast passes: one OR-accumulated bit per chunk (no positions); most tiles stop here.
+  // stride 4: a chunk's samples are its four dwords (the grid: bytes 0, 6, 12).  Two
+  // chunks per step, their bitmap reads issued before the first test (one LDS round
+  // trip per step, not one per probe)
+  __device__ __forceinline__ uint32_t fast_pairs(const ScanTile& c) const {
+    constexpr int kPer = QS == 4 ? 4 : 3;
+    const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
+    uint32_t chit = 0;
+#pragma unroll
+    for (int v = 0; v < (ABL(c, 4) ? 0 : 8); v += 2) {
+      const uint32_t ca = ((uint32_t)v + rot) & 7u, cb = ((uint32_t)v + 1u + rot) & 7u;
+      const uint4 xa = lane_chunk(s_tile, c, ca), xb = lane_chunk(s_tile, c, cb);
+      uint32_t g[2 * kPer];
+      if constexpr (QS == 4) {
+        g[0] = xa.x; g[1] = xa.y; g[2] = xa.z; g[3] = xa.w;
+        g[4] = xb.x; g[5] = xb.y; g[6] = xb.z; g[7] = xb.w;
+      } else {
+        g[0] = xa.x; g[1] = __builtin_amdgcn_alignbyte(xa.z, xa.y, 2u); g[2] = xa.w;
+        g[3] = xb.x; g[4] = __builtin_amdgcn_alignbyte(xb.z, xb.y, 2u); g[5] = xb.w;
+      }
+      Hash r[2 * kPer];
+      uint32_t w[2 * kPer];
+#pragma unroll
+      for (int k = 0; k < 2 * kPer; ++k) r[k] = hash(g[k]);
+#pragma unroll
+      for (int k = 0; k < 2 * kPer; ++k) w[k] = word(r[k]);
+      uint32_t acc_a = 0, acc_b = 0;
+#pragma unroll
+      for (int k = 0; k < 2 * kPer; ++k) {
+        const uint32_t t = test(w[k], r[k]);
+        if (k < kPer) acc_a |= t; else acc_b |= t;
+      }
+      chit |= ((acc_a & 1u) << ca) | ((acc_b & 1u) << cb);
+    }
+    return chit;
+  }
+  __device__ __forceinline__ uint32_t fast_chunks(const ScanTile& c) const {  // every other stride
+    const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
+    uint32_t chit = 0;
+#pragma unroll
+    for (int v = 0; v < (ABL(c, 4) ? 0 : 8); ++v) {
+      const uint32_t ch = ((uint32_t)v + rot) & 7u;
+      uint32_t acc = 0;
+      chunk_grams(c, ch, [&](uint32_t g, int) __attribute__((always_inline)) { acc |= hbits(g); });
+      chit |= (acc & 1u) << ch;
+    }
+    return chit;
+  }
+  // chunks with a possible hit (chit): the sample positions (past the tile's end clipped)
+  __device__ __forceinline__ void positions(const ScanTile& c, uint32_t chit, uint32_t (&hq)[4]) const {
+    for (uint32_t m = chit; m; m &= m - 1u) {
+      const uint32_t ch = (uint32_t)__builtin_ctz(m);
+      uint32_t hm = 0;
+      chunk_grams(c, ch, [&](uint32_t g, int pos) __attribute__((always_inline)) { hm |= (hbits(g) & 1u) << pos; });
+      or_quad(hq, ch >> 1, clip_chunk(c, hm, ch) << ((ch & 1u) * 16u));
+    }
+  }
+  // the tile's probe: every sample of my bytes
+  __device__ __forceinline__ void run(const ScanTile& c, uint32_t* s_list, uint32_t nlines, uint32_t (&hq)[4],
+                                      uint32_t& xh) const {
+    if constexpr (TWO) {
+      two_level(c, s_list, nlines, hq, xh);
+    } else {
+      const uint32_t chit = (QS == 4 || QS == 6) ? fast_pairs(c) : fast_chunks(c);
+      if (__any(chit != 0)) positions(c, chit, hq);
+    }
+  }
+};
+// short needles: every anchor byte whose dword passes a pre-check is a hit (its
+// bucket entries name the anchor's offset in the needle); anchors are rare
+__device__ __forceinline__ void anchored_hits(const DevPatterns& P, const uint8_t* s_tile, const ScanTile& c, uint32_t anc,
+                                              uint32_t pat, uint32_t afold, uint32_t (&hq)[4]) {
+  const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
+  const uint32_t npre = P.qf_anc_n, fold = P.qf_fold;
+  for (uint32_t cm = anc; cm; cm &= cm - 1u) {
+    const uint32_t ch = (uint32_t)__builtin_ctz(cm);
+    const uint4 x = lane_chunk(s_tile, c, ch);
+    uint32_t am = 0;
+    for (uint32_t e = clip_chunk(c, eq_mask16(afold ? or4(x, afold) : x, pat), ch); e; e &= e - 1u) {
+      const uint32_t pos = c.my0 + 16u * ch + (uint32_t)__builtin_ctz(e);
+      const uint32_t w = __builtin_amdgcn_alignbyte(s32[(pos >> 2) + 1], s32[pos >> 2], pos & 3u) | fold;
+      bool ok = false;
+      for (uint32_t j = 0; j < npre; ++j) ok |= (w & P.qf_anc_pre[2 * j + 1]) == P.qf_anc_pre[2 * j];
+      am |= ok ? 1u << (pos & 15u) : 0u;
+    }
+    or_quad(hq, ch >> 1, am << ((ch & 1u) * 16u));
+  }
+}
+// ---- the tile's hits -> its tile-owned slots (u16 tile offsets, no atomics); only a tile
+// with more than kHitSlots hits spills the rest to the global list.  Returns the slots used.
+__device__ __forceinline__ uint32_t emit_hits(const RunArgs& a, const ScanTile& c, const uint32_t (&hq)[4], uint32_t xh) {
+  const uint32_t nh = (uint32_t)(__popc(hq[0]) + __popc(hq[1]) + __popc(hq[2]) + __popc(hq[3])) + (xh != kNoHit ? 1u : 0u);
+  const uint32_t ih = wave_incl_scan_add(nh, c.lane);
+  const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)ih, 63);
+  uint32_t ob = 0;
+  if (tot > kHitSlots) {
+    if (c.lane == 63) ob = atomicAdd(&a.counters[kCtrHits], tot - kHitSlots);
+    ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, 63);
+  }
+  uint16_t* hs = a.hslots + (size_t)c.tile * kHitSlots;
+  uint32_t k = ih - nh;
+  auto put = [&](uint32_t off) __attribute__((always_inline)) {  // hit k of the tile, at tile offset off
+    if (k < kHitSlots) {
+      hs[k] = (uint16_t)off;
+    } else if ((uint64_t)ob + (k - kHitSlots) < a.qhits_cap) {
+      a.qhits[ob + (k - kHitSlots)] = c.sd.base + (uint64_t)c.rel_lo + off;
+    } else {
+      atomicOr(&a.counters[kCtrHitsOver], 1u);
+    }
+    ++k;
+  };
+  if (xh != kNoHit) put(xh);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    for (uint32_t m = hq[q]; m; m &= m - 1u) put(c.my0 + 32u * q + (uint32_t)__builtin_ctz(m));
+  return tot < kHitSlots ? tot : kHitSlots;
+}
+
+// ---- per-tile record: the line slots and the TileStat.
+// The number of store instructions per tile is fixed on every path: one or two slot stores
+// here (lanes past the units dropped by the descriptor), the group's TileStat store, and in
+// the planned plain scan plan_tile's two run stores and one plan store; k_scan's dummy
+// store before its loop gives the first tile the same count behind its prefetch.
+// A tile's line slots: one line start -> the slot in its TileStat (kTsInline); two or
+// more -> appended to the wave's own chunk of the pool (RunArgs::wave_pool, round 6: a
+// sequential stream of whole lines per wave, where the 1,152-B-stride record regions
+// took a 128-B store per tile however few its slots), 16-B aligned, TileStat bit 0 and
+// pool_base as for a dense tile (whose slots the line list wrote to the pool itself).
+// 16 B per lane: narrower per-lane stores cost several times more per byte.
+struct WavePool {
+  uint32_t cur = 0, end = 0;  // the wave's pool chunk (wave_pool): next free slot, end
+};
+struct TileTotals {     // (wave-uniform)
+  uint32_t pq;          // parsed | since_ok << 16 of the lines starting here
+  bool defer, hit;      // some line deferred; some line holds the fused literal
+  uint32_t carry;       // the furthest literal hit in the carried-in line (+ 1 + kCarryBias)
+  uint32_t tile_hits;   // general sets: hit slots used
+};
+// one reduction for both counts (each <= 8,193 per tile: 16 bits apiece, no carry from
+// the low half) and a ballot for the deferred lines, whose count nothing reads
+// (at most one line per lane -- 64 lines or fewer: two ballots' popcounts)
+__device__ __forceinline__ uint32_t packed_counts(const LineCounts& n, uint32_t nlines) {
+  return nlines <= 64u ? (uint32_t)__popcll(__ballot(n.parsed != 0u)) | ((uint32_t)__popcll(__ballot(n.since != 0u)) << 16)
+                       : wave_sum(n.parsed | (n.since << 16));
+}
+// GEN keeps the group's TileStats in a register quad (stv: lane k holds TileStat k; LDS is
+// what bounds its occupancy), the plain / literal scans in LDS (gstat; a quad there spills).
+template <int MODE>
+__device__ __forceinline__ void store_record(const RunArgs& a, const ScanTile& c, const TileStarts& tl, uint32_t agg,
+                                             const TileTotals& t, const uint32_t* s_list, WavePool& wp, uint4& stv,
+                                             uint4* gstat) {
+  constexpr bool GEN = MODE == kScanGen;
+  typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+  const uint32_t nlines = tl.nlines;
+  const bool dense = tl.dense;
+  const bool inl = !dense && nlines == 1u;
+  const bool pooled = a.wave_pool && !dense && nlines >= 2u;
+  // (timing builds: KLF_ABL 65536 drops only the slot stores, 131072 only the TileStat stores)
+  const bool no_slots = (c.abl && !(KLF_ABL & (65536 | 131072))) || ABL(c, 65536);
+  uint32_t pb = dense ? tl.pool_base : 0u, nunits = 0;
+  uint32_t* sdst = a.slots + (size_t)c.tile * kRecStride;  // the record region (a.wave_pool == 0: unit 0 the TileStat copy)
+  if (pooled && !no_slots) {
+    // 16-B granules; a run of 16 slots or more starts on a 128-B line and fills whole
+    // lines (a run straddling lines left partly written lines behind: C3 +1.6 %, r6f)
+    const bool whole = nlines > 12u;
+    const uint32_t need = whole ? (nlines + 31u) & ~31u : (nlines + 3u) & ~3u;
+    if (whole) wp.cur = (wp.cur + 31u) & ~31u;  // (chunks start 128-B aligned: see below)
+    if (wp.cur + need > wp.end) {  // (wave-uniform) a new chunk
+      const uint32_t ch = need > a.pool_chunk ? need : a.pool_chunk;
+      uint32_t b = 0;
+      if (c.lane == 0) b = atomicAdd(&a.counters[kCtrPool], ch);
+      b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+      wp.cur = b;
+      wp.end = (uint64_t)b + ch <= a.pool_cap ? b + ch : b;  // (past the pool: no room, the run is redone)
+      if (wp.end == b && c.lane == 0) atomicOr(a.counters + 2, 1u);
+    }
+    if (wp.cur + need <= wp.end) {
+      pb = wp.cur;
+      wp.cur += need;
+      nunits = need / 4u;
+      sdst = a.pool + pb;
+    }
+  } else if (!a.wave_pool && !no_slots && !dense && nlines > 1u) {
+    nunits = ((kRecHead + nlines + 31u) & ~31u) / 4u;  // the record region (whole 128-B lines)
+  }
+  const uint32_t w0 = agg, w1 = (dense || pooled) ? pb : (inl ? s_list[0] : 0u);
+  const uint32_t w2 = t.pq;
+  const uint32_t w3 = (((dense || (pooled && nunits)) ? 1u : 0u) | (t.carry ? 2u : 0u) | (t.defer ? 4u : 0u) |
+                       (t.hit ? 8u : 0u) | (inl ? kTsInline : 0u)) |
+                      ((uint32_t)(uint16_t)(GEN ? t.tile_hits : t.carry) << 16);  // GEN: hit slots used
+  const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(sdst, 0, (int)(nunits * 16u), 0x00020000);
+  const uint32_t ushift = a.wave_pool ? 0u : 1u;  // (the record region: unit 0 the TileStat)
+  for (uint32_t u = (uint32_t)c.lane; u < (nunits > 64u ? 128u : 64u); u += 64) {  // one or two stores
+    const uint32_t us = u - ushift;  // (u = 0 of a record: -1)
+    const uint32_t li = u < ushift ? 0u : (4u * us < (uint32_t)kSlotStride - 4u ? 4u * us : (uint32_t)kSlotStride - 4u);
+    const uint4 sl = *reinterpret_cast<const uint4*>(s_list + li);
+    const u32x4v v = u >= ushift ? u32x4v{sl.x, sl.y, sl.z, sl.w} : u32x4v{w0, w1, w2, w3};
+    __builtin_amdgcn_raw_buffer_store_b128(v, rrs, 16u * u, 0, 0);
+  }
+  // the group's TileStats, one 128-B store at its last tile (lanes past it dropped)
+  const uint32_t gk = c.tile % kScanGroup, g0 = c.tile - gk;
+  if (GEN) {
+    if ((uint32_t)c.lane == gk) stv = make_uint4(w0, w1, w2, w3);
+  } else {
+    if (c.lane == 0) gstat[gk] = make_uint4(w0, w1, w2, w3);
+    wave_lds_sync();
+  }
+  const bool gend = gk == kScanGroup - 1 || c.tile + 1 >= a.ntiles;
+  const uint32_t ng = a.ntiles - g0 < kScanGroup ? a.ntiles - g0 : kScanGroup;
+  const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
+      a.tstat + g0, 0, (gend && (!c.abl || (KLF_ABL & 65536))) && !ABL(c, 131072) ? (int)(16u * ng) : 0, 0x00020000);
+  const uint4 gs = GEN ? stv : gstat[c.lane & (kScanGroup - 1)];
+  __builtin_amdgcn_raw_buffer_store_b128(u32x4v{gs.x, gs.y, gs.z, gs.w}, srs, 16u * (uint32_t)c.lane, 0, 0);
+}
+
+// The tile descriptors come in as separate __restrict__ const parameters so that their
+// (wave-uniform) reads compile to scalar loads: a vector load of them would be ordered
+// behind the in-flight prefetch by vmcnt and stall every tile on the next tile's bytes.
+// General sets: QS sampling stride, QK bits per gram, QQ gram bytes (3 or 4), QA (stride 8
+// only) the short needles' anchor test (DevPatterns::qf_anc_*).
 template <int MODE, int QS, int QK, int QQ = 4, bool QA = false, bool FUSE = false>
 __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void k_scan(RunArgs a, const uint32_t* __restrict__ tseg,
                                                                const SegDesc* __restrict__ segs) {
@@ -511,9 +1358,7 @@ __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void
   constexpr bool LIT = MODE == kScanLit;
   constexpr bool GEN = MODE == kScanGen;
   constexpr bool ANC = GEN && QA;
-  static_assert(QQ == 3 || QQ == 4, "3- or 4-byte grams");
   constexpr int kWaves = kThreads / 64;
-  constexpr int kRows = kTile / 1024;  // 1 KiB rows: 16 B per lane per row
   // (FUSE: 16 B of front pad, which copy_tile_runs' unaligned windows read)
   constexpr int kPad = FUSE ? 16 : 0;
   __shared__ __attribute__((aligned(16))) uint8_t s_tile_all[kWaves][kPad + kTile + kHalo];
@@ -521,45 +1366,22 @@ __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void
   __shared__ __attribute__((aligned(16))) uint16_t s_fmap_all[FUSE ? kWaves : 1][FUSE ? kTcChunks : 8];
   __shared__ __attribute__((aligned(16))) uint32_t s_list_all[kWaves][kSlotStride];
   __shared__ __attribute__((aligned(16))) uint32_t s_lit[kMaxFusedLiteral / 4 + 1];  // literal, zero padded
-  // the TileStats of the wave's current tile group: LDS for the plain / literal scans (a
-  // register quad there spills), a register quad for GEN (LDS is what bounds its occupancy)
+  // the TileStats of the wave's current tile group (store_record)
   __shared__ uint4 s_gstat[GEN ? 1 : kWaves][kScanGroup];
   __shared__ uint32_t s_qf[GEN ? kQfWords : 1];  // q-gram bitmap of the needles
-  __shared__ uint32_t s_h2[GEN ? kWaves : 1][1];  // a tile's inline hits (kTsHitInline): two u16
   // wv is wave-uniform; readfirstlane tells the compiler so (tile indices stay in SGPRs and
   // the descriptor reads stay scalar loads)
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
   uint8_t* s_tile = s_tile_all[wv] + kPad;
   uint32_t* s_list = s_list_all[wv];
-  uint32_t* err_flag = a.counters + 2;
   for (uint32_t i = t; i < kMaxFusedLiteral / 4 + 1; i += kThreads)
     s_lit[i] = (LIT && i < (a.lit_len + 3) / 4) ? a.lit_words[i] : 0u;
   if (GEN)
     for (uint32_t i = t; i < kQfWords; i += kThreads) s_qf[i] = a.pats.qf_bitmap[i];
-  __syncthreads();  // the kernel's only block barrier
+  __syncthreads();  // the kernel's only block barrier: from here on a wave works alone
   const uint32_t nwaves = gridDim.x * kWaves;
-  // Timing builds (KLF_ABL != 0, scripts/variant.sh): the first launch is the full scan;
-  // from the second launch on (a wave knows once every wave of an earlier launch has
-  // finished) the ablated scan runs and stores nothing, so the first launch's records feed
-  // the downstream kernels (identical batches) and no ablation can misdirect them.
-  // KLF_ABL bits: 2 no literal anchor test, 64 staging + any-test only, 1 no timestamp
-  // parse, 128 no line list / parse / literal, 4 no prefilter fast pass, 8 prefilter
-  // probes only; 4096 = nothing removed (the scan without its stores).
   const bool abl = (KLF_ABL != 0) &&
                    __hip_atomic_load(&g_abl_waves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nwaves;
-#define ABL(x) ((KLF_ABL & (x)) && abl)
-
-  // the prefetch registers are named (an array here was put on the scratch stack)
-  static_assert(kRows == 8, "KLF_ROWS lists the 8 prefetch rows");
-#define KLF_ROWS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-#define KLF_DECL(r) uint4 pf##r;
-  KLF_ROWS(KLF_DECL)
-#undef KLF_DECL
-// non-temporal prefetch loads in the literal / general scans (not the plain one: C3's
-// k_tcopy re-reads the input, 5.15 -> 5.18 ms with them)
-#define KLF_LOAD(r) pf##r = (KLF_SCAN_NT && MODE != kScanPlain) ? ld_nt(&gp[r * 64 + lane]) : gp[r * 64 + lane];
-#define KLF_STORE(r) l[r * 64 + lane] = pf##r;
-  uint4 pfh = make_uint4(0, 0, 0, 0);
   // A wave takes groups of kScanGroup consecutive tiles (group g, g + nwaves, ...): their
   // TileStats go out together as one whole-line store into the compact tstat array.
   // (FUSE: the wave's own range of consecutive tiles instead)
@@ -575,14 +1397,13 @@ __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void
   // nwaves tiles stays inside one stream for all but the last tiles of a long stream, so
   // the dependent descriptor loads (tseg -> segs, scalar-cache misses at this stride) leave
   // the path that issues the next prefetch.
+  TileRows pf;
   uint32_t pf_s = 0;
   SegDesc pf_sd{};
   if (tile < a.ntiles) {
     pf_s = tseg[tile];
     pf_sd = segs[pf_s];
-    const uint4* gp = reinterpret_cast<const uint4*>(a.bytes + pf_sd.base + (uint64_t)(tile - pf_sd.tile0) * kTile);
-    KLF_ROWS(KLF_LOAD)
-    if (lane < kHalo / 16) pfh = (KLF_SCAN_NT && MODE != kScanPlain) ? ld_nt(&gp[kTile / 16 + lane]) : gp[kTile / 16 + lane];
+    pf.load<MODE>(tile_bytes(a.bytes, pf_sd, tile), lane);
   }
   // Each tile ends with exactly one unconditional store instruction (the first two 128-B
   // lines of its record region, through a buffer descriptor so that an ablated launch can
@@ -594,799 +1415,80 @@ __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void
     __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0x7FFF0000u, 0, 0);
   }
   bool any_defer = false;
-  uint32_t wp_cur = 0, wp_end = 0;  // the wave's pool chunk (wave_pool): next free slot, end
-  // FUSE state of the wave's range (wave-uniform): whether the line open at the current tile
-  // start is decided (a line started in this range's part of the stream, or the part began
-  // at the stream's start), that line's kept bit and content start - the tile start (f_sat),
-  // the output position, the current extent
-  bool fz_known = false, fz_sel = false, fz_res_set = false;
-  int32_t fz_crel = -1;
-  uint64_t fz_obase = 0, fz_estart = 0, fz_res = 0, fz_part = 0, fz_rbase = 0;
-  uint32_t fz_ext = 0;
+  WavePool wp;
+  FuseState fz;
   if (FUSE && tile < tile_end) {
-    fz_rbase = pf_sd.base + (uint64_t)(tile - pf_sd.tile0) * kTile;
-    fz_ext = a.fuse_ext0[gw];
+    fz.rbase = pf_sd.base + (uint64_t)(tile - pf_sd.tile0) * kTile;
+    fz.ext = a.fuse_ext0[gw];
   }
-  // closes the current extent (a range part that saw no line start: all of it is left to
-  // k_fcarry, the extent empty at its end)
-  auto fz_close = [&]() __attribute__((always_inline)) {
-    if (!fz_res_set) {
-      fz_res = fz_part;
-      fz_res_set = true;
-      fz_estart = fz_obase = fz_rbase + fz_part;
-    }
-    if (lane == 0) {
-      a.fuse_ext[2 * (size_t)fz_ext] = fz_estart;
-      a.fuse_ext[2 * (size_t)fz_ext + 1] = fz_obase - fz_estart;
-    }
-  };
   for (; tile < tile_end; tile = next_tile(tile)) {
-    const uint32_t s = pf_s;
-    const SegDesc sd = pf_sd;
-    const int64_t rel_lo = (int64_t)(tile - sd.tile0) * kTile;
-    const int64_t seg_len = (int64_t)sd.len;
-    const int32_t tile_len = (int32_t)(seg_len - rel_lo < kTile ? seg_len - rel_lo : kTile);
-    const bool first = rel_lo == 0;
-    const bool last = rel_lo + kTile >= seg_len;
-    const uint8_t* segp = a.bytes + sd.base;
-
+    const ScanTile c = scan_tile(a.bytes, tile, pf_s, pf_sd, lane, abl);
     // ---- stage this tile in the wave's LDS region, then start loading the next one ----
-    if (KLF_SCAN_PRIO) __builtin_amdgcn_s_setprio(KLF_SCAN_PRIO);  // A/B: the prefetch issue first
-    {
-      uint4* l = reinterpret_cast<uint4*>(s_tile);
-      KLF_ROWS(KLF_STORE)
-      if (lane < kHalo / 16) l[kTile / 16 + lane] = pfh;
-      const uint32_t nx = next_tile(tile);
-      if (nx < tile_end) {
-        if (nx - sd.tile0 >= sd.ntiles) {
-          pf_s = tseg[nx];
-          pf_sd = segs[pf_s];
-        }
-        const uint4* gp = reinterpret_cast<const uint4*>(a.bytes + pf_sd.base + (uint64_t)(nx - pf_sd.tile0) * kTile);
-        KLF_ROWS(KLF_LOAD)
-        if (lane < kHalo / 16) pfh = (KLF_SCAN_NT && MODE != kScanPlain) ? ld_nt(&gp[kTile / 16 + lane]) : gp[kTile / 16 + lane];
+    pf.store(s_tile, lane);
+    const uint32_t nx = next_tile(tile);
+    if (nx < tile_end) {
+      if (nx - c.sd.tile0 >= c.sd.ntiles) {
+        pf_s = tseg[nx];
+        pf_sd = segs[pf_s];
       }
+      pf.load<MODE>(tile_bytes(a.bytes, pf_sd, nx), lane);
     }
-    if (KLF_SCAN_PRIO) __builtin_amdgcn_s_setprio(0);
     wave_lds_sync();
 
-    // ---- any-tests over my 128 bytes: 8 chunks of 16 B, read rotated (chunk (v + lane/2)
-    // mod 8) so that every 16-lane group of a ds_read_b128 covers all 64 banks once ----
-    const uint32_t my0 = (uint32_t)lane * kLaneBytes;
-    const int nvalid_s = tile_len - (int)my0;
-    const int nvalid = nvalid_s <= 0 ? 0 : (nvalid_s >= kLaneBytes ? kLaneBytes : nvalid_s);
     // the byte of the anchor test: the fused literal's rarest byte, or the short needles'
     // anchor (loose short needles: bytes tested OR 0x20)
     const uint32_t pat = ANC ? a.pats.qf_anc_byte : a.lit_anchor_byte * 0x01010101u;
     const uint32_t afold = ANC ? a.pats.qf_anc_fold : 0u;
-    auto or4 = [](const uint4& x, uint32_t f) { return make_uint4(x.x | f, x.y | f, x.z | f, x.w | f); };
-    uint32_t nlc = 0, anc = 0;
-    {
-      const uint32_t rot = ((uint32_t)lane >> 1) & 7u;
-      // KLF_ANY_BATCH reads in flight before the first test (8: one LDS round trip, not
-      // eight; 4: two round trips, 16 fewer VGPRs)
-#pragma unroll
-      for (int v0 = 0; v0 < 8; v0 += KLF_ANY_BATCH) {
-        uint4 xs[KLF_ANY_BATCH];
-#pragma unroll
-        for (int v = 0; v < KLF_ANY_BATCH; ++v)
-          xs[v] = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * (((uint32_t)(v0 + v) + rot) & 7u));
-#pragma unroll
-        for (int v = 0; v < KLF_ANY_BATCH; ++v) {
-          const uint32_t c = ((uint32_t)(v0 + v) + rot) & 7u;
-          nlc |= any_eq16(xs[v], 0x0A0A0A0Au) ? (1u << c) : 0u;
-          if (LIT && !ABL(2)) anc |= any_eq16(xs[v], pat) ? (1u << c) : 0u;
-          if (ANC) anc |= any_eq16(afold ? or4(xs[v], afold) : xs[v], pat) ? (1u << c) : 0u;
-        }
-      }
-      if (nvalid < kLaneBytes) {
-        const uint32_t vm = (1u << ((nvalid + 15) >> 4)) - 1u;
-        nlc &= vm;
-        anc &= vm;
-      }
-    }
-    if (ABL(64)) {  // timing build: staging + any-test only
-      asm volatile("" ::"v"(nlc | anc) : "memory");
+    const AnyHits any = any_tests<LIT, ANC>(s_tile, c, pat, afold);
+    if (ABL(c, 64)) {  // timing build: staging + any-test only
+      asm volatile("" ::"v"(any.nlc | any.anc) : "memory");
       continue;
     }
-    auto clip = [&](uint32_t e, uint32_t c) -> uint32_t {  // bytes of chunk c past the tile's end
-      const int nv = nvalid - 16 * (int)c;
-      return nv >= 16 ? e : (nv <= 0 ? 0u : (e & ((1u << nv) - 1u)));
-    };
-    // ---- exact line-end positions in the chunks that hit: a 128-bit event mask ----
-    uint32_t em[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t m = nlc; m; m &= m - 1u) {
-      const uint32_t c = (uint32_t)__builtin_ctz(m);
-      const uint4 x = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * c);
-      const uint32_t e = clip(KLF_NL_MASK ? eq_mask16_nl(x) : eq_mask16(x, 0x0A0A0A0Au), c) << ((c & 1u) * 16u);
-      const uint32_t q = c >> 1;
-      em[0] |= q == 0 ? e : 0u;
-      em[1] |= q == 1 ? e : 0u;
-      em[2] |= q == 2 ? e : 0u;
-      em[3] |= q == 3 ? e : 0u;
-    }
-    // the stream's end is an event too (it closes the last line); it starts no line
-    uint32_t st[4] = {em[0], em[1], em[2], em[3]};
-    if (last && nvalid > 0 && (int)my0 + nvalid == tile_len) {
-      const uint32_t eb = (uint32_t)nvalid - 1u, q = eb >> 5, bit = 1u << (eb & 31u);
-      bool nl_at_end = false;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if ((uint32_t)k == q) {
-          nl_at_end = (em[k] & bit) != 0u;
-          em[k] |= bit;
-          st[k] &= ~bit;
-        }
-      if (!abl) a.segout[s].frag = nl_at_end ? 0 : 1;
-    }
-    const uint32_t cnt = (uint32_t)(__popc(em[0]) + __popc(em[1]) + __popc(em[2]) + __popc(em[3]));
-    // (at most one event per lane -- lines of 128 B and more: a ballot's rank is the scan)
-    const uint32_t incl = (KLF_SCAN_BALLOT && !__any(cnt > 1u))
-                              ? cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(__ballot(cnt != 0u) >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)__ballot(cnt != 0u), 0u))
-                              : wave_incl_scan_add(cnt, lane);
-    const uint32_t agg = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    // Local line k = the line after the tile's k-th event (k = 0: the line open at the
-    // tile start).  Lines starting here: k in [k0, k1), slot j = k - k0.
-    const uint32_t k0 = first ? 0 : 1;
-    const uint32_t k1 = last ? agg : agg + 1;
-    const uint32_t nlines = k1 > k0 ? k1 - k0 : 0;
-    const bool dense = nlines > (uint32_t)kSlots;
-    uint32_t pool_base = 0;
-    if (dense) {
-      uint32_t pb = 0;
-      if (lane == 0 && !abl) {
-        pb = atomicAdd(&a.counters[kCtrPool], (nlines + 31u) & ~31u);  // (whole 128-B lines: the waves' chunks stay aligned)
-        if ((uint64_t)pb + nlines > a.pool_cap) atomicOr(err_flag, 1u);
-      }
-      pool_base = (uint32_t)__builtin_amdgcn_readlane((int)pb, 0);
-    }
-    const bool pool_ok = !dense || (uint64_t)pool_base + nlines <= a.pool_cap;
-    uint32_t* const trec = a.slots + (size_t)tile * kRecStride;  // this tile's record region
-    uint32_t* gslot = dense ? a.pool + pool_base : trec + kRecHead;
+    const LineEvents ev = line_events(s_tile, c, any.nlc, a.segout);
+    const TileStarts tl = tile_starts(a, c, ev.agg);
 
-    // The per-tile work on the line list, instantiated for the LDS list (normal tiles) and
-    // the global pool (dense tiles).
-    uint32_t n_parsed = 0, n_since = 0, n_defer = 0, carry = 0, n_hit = 0;
-    auto work = [&](uint32_t* list) __attribute__((always_inline)) {
-      // ---- line starts -> list[j] = start offset in the tile ----
-      if (first && lane == 0) list[0] = 0u;
-      {
-        uint32_t kk = incl - cnt;  // events before my bytes
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          for (uint32_t ev = em[q]; ev; ev &= ev - 1u) {
-            const uint32_t b = (uint32_t)__builtin_ctz(ev);
-            ++kk;
-            if ((st[q] >> b) & 1u) list[kk - k0] = my0 + 32u * q + b + 1u;
-          }
-        }
-      }
-      if (dense) __threadfence_block();
-      wave_lds_sync();
-      // ---- timestamp + since: one line per lane ----
-      for (uint32_t b0 = 0; b0 < nlines; b0 += 64) {
-        const uint32_t j = b0 + (uint32_t)lane;
-        if (j < nlines) {
-          const uint32_t off = list[j];
-          bool so = false, fast = false;
-          if (ABL(1)) {
-            fast = so = true;
-          } else if (rel_lo + (int64_t)off + 31 <= seg_len) {
-            fast = parse_fast(s_tile, off, a.since_dig, so);
-          }
-          if (FUSE && !fast) {  // the one-pass compaction decides every line here: Go time.Parse
-            TsResult tr;
-            uint32_t plen = 0;
-            const bool ok = parse_line_prefix(GlobalBytes{segp, rel_lo + (int64_t)off, seg_len}, tr, plen);
-            const bool so2 = ok && !time_before(tr.sec, tr.nsec, a.since_sec, a.since_nsec);
-            list[j] = off | ((uint32_t)make_meta(ok, so2, ok ? plen : 0u) << 16);
-            if (ok && plen >= kPlenEscape) atomicOr(&a.counters[kCtrFuseBad], 1u);  // (a prefix longer than the meta holds)
-            n_parsed += ok ? 1u : 0u;
-            n_since += so2 ? 1u : 0u;
-          } else {
-            list[j] = fast ? (off | ((uint32_t)make_meta(true, so, 31) << 16)) : (off | kSlotDefer);
-            n_parsed += fast ? 1u : 0u;
-            n_since += (fast && so) ? 1u : 0u;
-            n_defer += fast ? 0u : 1u;
-          }
-        }
-      }
-      // ---- planned dense compaction: the tile's own kept runs and aggregate (FAgg above).
-      // Two rounds of 64 lines, each ending in one buffer store of the runs (lanes without a
-      // run, or past the record, dropped) and the plan in one more: a fixed store count per
-      // tile (see the record stores below).  Tiles with more lines leave their runs to
-      // k_tcopy (kRunsRecompute).
-      if constexpr (MODE == kScanPlain && FUSE) {
-        // ---- one-pass compaction: this tile's kept runs (the carried-in line's, then the
-        // lines starting here), copied to the range's output at once (a dense tile voids
-        // the pass) ----
-        if (!dense) {
-        wave_lds_sync();
-        if (__any(n_defer != 0) && lane == 0) a.counters[kCtrFuseBad] = 1u;  // decided later: rerun
-        const uint64_t tin = sd.base + (uint64_t)rel_lo;  // the tile's input = output position
-        if (first) {  // a stream starts here: nothing carried in
-          if (tile != range_t0) {
-            fz_close();
-            ++fz_ext;
-          } else {
-            fz_res_set = true;
-          }
-          fz_known = true;
-          fz_sel = false;
-          fz_crel = -1;
-          fz_obase = fz_estart = tin;
-          fz_part = 0;
-        }
-        const uint32_t span = nlines ? (list[0] & kSlotOff) : (uint32_t)tile_len;
-        uint32_t clen = 0, csrc = 0;
-        if (fz_known) {
-          clen = f_carried(span, fz_sel, fz_crel);
-          csrc = fz_crel > 0 ? (uint32_t)fz_crel : 0u;
-        } else if (nlines) {  // the range's first line start: the bytes before it are k_fcarry's
-          fz_res = fz_part + span;
-          fz_res_set = true;
-          fz_obase = fz_estart = tin + span;
-        }
-        uint32_t* s_frun = s_frun_all[wv];
-        uint32_t nr = 0, dacc = 0, lsel = 0;
-        int32_t lcrel = -1;
-        for (uint32_t b0 = 0; b0 < nlines; b0 += 64) {
-          const uint32_t j = b0 + (uint32_t)lane;
-          uint32_t src = 0, len = 0;
-          if (j < nlines) {
-            const uint32_t v = list[j], off = v & kSlotOff, mt = v >> 16;
-            const bool sel = !(v & kSlotDefer) && (mt & Meta::kParsed) && (mt & Meta::kSince);
-            const uint32_t c = off + (mt >> 2);
-            const uint32_t e = j + 1 < nlines ? (list[j + 1] & kSlotOff) : (uint32_t)tile_len;
-            if (sel && e > c) { src = c; len = e - c; }
-            if (j + 1 == nlines) { lsel = sel ? 1u : 0u; lcrel = f_sat((int32_t)c - tile_len); }
-          }
-          const uint32_t incl = wave_incl_scan_add(len, lane);
-          const uint64_t bm = __ballot(len != 0);
-          const uint32_t idx = nr + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
-          if (len) s_frun[1 + idx] = src | ((clen + dacc + incl - len) << 16);
-          nr += (uint32_t)__popcll(bm);
-          dacc += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        if (clen && lane == 0) s_frun[0] = csrc;  // (output offset 0)
-        const uint32_t kept = clen + dacc;
-        if (kept) {
-          if (fz_obase + kept + 16 > a.out_cap) {
-            if (lane == 0) a.counters[kCtrFuseBad] = 1u;
-          } else {
-            copy_tile_runs(s_tile, clen ? s_frun : s_frun + 1, s_fmap_all[wv], nr + (clen ? 1u : 0u), kept, fz_obase,
-                           a.out, lane);
-          }
-          fz_obase += kept;
-        }
-        if (nlines) {
-          const uint32_t lastl = (nlines - 1u) & 63u;
-          fz_sel = __builtin_amdgcn_readlane((int)lsel, (int)lastl) != 0;
-          fz_crel = __builtin_amdgcn_readlane(lcrel, (int)lastl);
-          fz_known = true;
-        } else if (fz_known) {
-          fz_crel = f_sat(fz_crel - tile_len);
-        }
-        fz_part += (uint64_t)tile_len;
-        }
-      } else if constexpr (MODE == kScanPlain) {
-        if (a.plan_runs) {
-          if (dense) __threadfence_block();
-          wave_lds_sync();
-          typedef uint32_t u32x4p __attribute__((ext_vector_type(4)));
-          const bool fits = nlines <= 128u && !abl;
-          const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-              a.truns + (size_t)tile * kRunSlots, 0, fits ? kRunSlots * 4 : 0, 0x00020000);
-          uint32_t nr = 0, dacc = 0, ns = 0, lsel = 0;
-          int32_t lcrel = -1;
-          // one round of 64 lines: the run word and its store offset (dropped: none)
-          auto round = [&](uint32_t b0, uint32_t& w, uint32_t& o) __attribute__((always_inline)) {
-            const uint32_t j = b0 + (uint32_t)lane;
-            uint32_t src = 0, len = 0;
-            bool sel = false, starts = false;
-            if (j < nlines) {
-              const uint32_t v = list[j], off = v & kSlotOff, mt = v >> 16;
-              sel = !(v & kSlotDefer) && (mt & Meta::kParsed) && (mt & Meta::kSince);
-              const uint32_t c = off + (mt >> 2);
-              const uint32_t e = j + 1 < nlines ? (list[j + 1] & kSlotOff) : (uint32_t)tile_len;
-              if (sel && e > c) { src = c; len = e - c; }
-              // (a line starting at the tile end -- the last byte is '\n' -- starts the next
-              // tile, whose list does not hold it: counted here, in its stream)
-              starts = off <= (uint32_t)tile_len;
-              if (j + 1 == nlines) { lsel = sel ? 1u : 0u; lcrel = f_sat((int32_t)c - tile_len); }
-            }
-            const uint32_t incl = wave_incl_scan_add(len, lane);
-            const uint64_t bm = __ballot(len != 0);
-            const uint32_t idx = nr + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
-            // slot 0 is the carried-in run's (k_cmove)
-            w = src | ((dacc + incl - len) << 16);
-            o = len ? 4u * (idx + 1u) : 0x7FFF0000u;
-            nr += (uint32_t)__popcll(bm);
-            dacc += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            ns += (uint32_t)__popcll(__ballot(sel && starts));
-          };
-          uint32_t w0 = 0, o0 = 0x7FFF0000u, w1 = 0, o1 = 0x7FFF0000u;
-          round(0u, w0, o0);
-          __builtin_amdgcn_raw_buffer_store_b32(w0, rr, o0, 0, 0);
-          if (nlines > 64u) round(64u, w1, o1);  // (its store issues either way: a fixed count)
-          __builtin_amdgcn_raw_buffer_store_b32(w1, rr, o1, 0, 0);
-          for (uint32_t b0 = 128u; b0 < nlines; b0 += 64) {  // (no runs stored)
-            uint32_t w, o;
-            round(b0, w, o);
-          }
-          const uint32_t lastl = nlines ? ((nlines - 1u) & 63u) : 0u;
-          const uint32_t psel = nlines ? (uint32_t)__builtin_amdgcn_readlane((int)lsel, (int)lastl) : 0u;
-          const int32_t pcrel = nlines ? __builtin_amdgcn_readlane(lcrel, (int)lastl) : -1;
-          const uint32_t span = nlines ? (list[0] & kSlotOff) : (uint32_t)tile_len;
-          const uint32_t px = (dacc & 0x3FFFu) | ((span & 0x3FFFu) << 14) | ((nlines ? 1u : 0u) << 28) | (psel << 29);
-          const uint32_t py = ((uint32_t)(uint16_t)(int16_t)pcrel) | (ns << 16);
-          const uint32_t pz = (fits && nr + 1u <= (uint32_t)kRunSlots) ? nr : (uint32_t)kRunsRecompute;
-          const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(a.trec + tile, 0, abl ? 0 : 16, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4p{px, py, pz, kPlanTag}, pr, lane ? 0x7FFF0000u : 0u, 0, 0);
-        }
-      }
-      // number of listed line starts at or before tile offset pos
-      auto starts_upto = [&](int32_t pos) __attribute__((always_inline)) -> int {
-        int lo = 0, hi = pos < 0 ? 0 : (int)nlines;  // pos < 0: in the carried-in line
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if ((list[mid] & kSlotOff) <= (uint32_t)pos) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-      };
-      // a final (literal) hit starting at tile offset pos -> its line's hit bit
-      auto attribute = [&](int32_t pos) __attribute__((always_inline)) {
-        const int lo = starts_upto(pos);
-        if (lo > 0) {  // the line starts in this tile: deferred lines are searched by k_fixup
-          const uint32_t v = list[lo - 1];
-          const uint32_t mt = v >> 16;
-          if (!(v & kSlotDefer) && (mt & Meta::kParsed) && (uint32_t)pos >= (v & kSlotOff) + (mt >> 2)) {
-            atomicOr(&list[lo - 1], kSlotHit);
-            ++n_hit;
-          }
-        } else {  // carried in from an earlier tile: k_scatter decides (furthest hit wins)
-          const uint32_t c1 = (uint32_t)(pos + 1 + (int32_t)kCarryBias);  // pos >= -kCarryBias
-          carry = carry > c1 ? carry : c1;
-        }
-      };
-      // ---- fused single-literal grep ----
-      // Anchor hits (the literal's rarest byte) name candidate starts p = anchor - ka.  A
-      // tile owns the starts inside it: anchors whose start lies in the previous tile are
-      // left to that tile, which scans its halo.
-      if (LIT) {
-        if (dense) __threadfence_block();
-        wave_lds_sync();
-        const uint32_t m = a.lit_len, ka = a.lit_anchor;
-        auto check = [&](int32_t pos) __attribute__((always_inline)) {
-          if (pos < 0 || pos >= tile_len || rel_lo + pos + (int64_t)m > seg_len) return;
-          bool eq = true;
-          if ((uint32_t)pos + m + 4 <= (uint32_t)(kTile + kHalo)) {  // 4 bytes per LDS read
-            const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
-            const uint32_t sh = (uint32_t)pos & 3u;
-            uint32_t wi = (uint32_t)pos >> 2;
-            uint32_t prev = s32[wi];
-            for (uint32_t k = 0; k < m && eq; k += 4) {
-              const uint32_t nx = s32[++wi];
-              const uint32_t got = __builtin_amdgcn_alignbyte(nx, prev, sh);
-              prev = nx;
-              const uint32_t nb = m - k < 4 ? m - k : 4;
-              const uint32_t msk = nb == 4 ? 0xFFFFFFFFu : ((1u << (8 * nb)) - 1);
-              eq = ((got ^ s_lit[k >> 2]) & msk) == 0;
-            }
-          } else {
-            const uint8_t* lit = reinterpret_cast<const uint8_t*>(s_lit);
-            for (uint32_t k = 0; k < m && eq; ++k) {
-              const uint32_t o = (uint32_t)pos + k;
-              const uint8_t c = o < (uint32_t)(kTile + kHalo) ? s_tile[o] : segp[rel_lo + o];
-              eq = c == lit[k];
-            }
-          }
-          if (!eq) return;
-          attribute(pos);
-        };
-        for (uint32_t cm = anc; cm; cm &= cm - 1u) {
-          const uint32_t c = (uint32_t)__builtin_ctz(cm);
-          const uint4 x = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * c);
-          for (uint32_t e = clip(eq_mask16(x, pat), c); e; e &= e - 1u)
-            check((int32_t)(my0 + 16u * c + (uint32_t)__builtin_ctz(e)) - (int32_t)ka);
-        }
-        if (lane == 63 && ka > 0 && !last) {  // halo anchors -> starts in this tile's tail
-          for (uint32_t jj = 0; jj < ka; ++jj) {
-            const int64_t q = rel_lo + kTile + jj;
-            if (q >= seg_len) break;
-            const uint8_t c = jj < (uint32_t)kHalo ? s_tile[kTile + jj] : segp[q];
-            if (c == a.lit_anchor_byte) check((int32_t)(kTile + jj) - (int32_t)ka);
-          }
-        }
-        carry = wave_max(carry);
-      }
-      if (dense) __threadfence_block();
-      wave_lds_sync();
-    };
-    if (ABL(128)) {  // timing build: no line list / parse / literal
-    } else if (!dense) {
-      work(s_list);
-    } else if (pool_ok && !abl) {
+    LineCounts n;
+    if (ABL(c, 128)) {  // timing build: no line list / parse / literal
+    } else if (!tl.dense) {
+      line_work<MODE, FUSE>(s_list, a, c, ev, tl, s_tile, s_lit, any.anc, pat, fz, tile == range_t0, s_frun_all[FUSE ? wv : 0],
+                            s_fmap_all[FUSE ? wv : 0], n);
+    } else if (tl.pool_ok && !abl) {
       if (FUSE && lane == 0) a.counters[kCtrFuseBad] = 1u;  // (a dense tile: the two-pass rerun)
-      work(gslot);
+      line_work<MODE, FUSE>(a.pool + tl.pool_base, a, c, ev, tl, s_tile, s_lit, any.anc, pat, fz, tile == range_t0,
+                            s_frun_all[FUSE ? wv : 0], s_fmap_all[FUSE ? wv : 0], n);
     }
 
     uint32_t tile_hits = 0;
-    bool hinl = false;  // GEN: the tile's hits inline (kTsHitInline)
-    uint32_t hit2 = 0;
-    // ---- general sets: fused q-gram prefilter ----
-    // Samples p = 0 mod QS of the tile (each needle's chosen window is q + QS - 1 long, so
-    // every occurrence spans exactly one sample whose gram lies in the window) probe the
-    // LDS bitmap (one word, two bits per gram).  The few bitmap hits are appended to a global list
-    // (one atomic per wave and tile) and verified by k_verify once the line index exists:
-    // the scan keeps no verification code, and the latency-bound bucket walks run with
-    // the whole GPU's parallelism.
-    if (GEN) {
-      const uint32_t fold = a.pats.qf_fold;
-      const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
-      // bit 0 of the result: gram g has all K bits of its bitmap word set (qf_f / qf_hash /
-      // qf_bits): the multiplies, the word read, and the bit positions as byte / word selects
-      // or low bits of the products (SDWA operands of the shifts)
-      struct Probe {
-        uint32_t h, p, m, a;  // a: byte offset of the bitmap word in LDS (qf_bucket * 4)
-      };
-      constexpr bool kMidIdx = QQ == 3 && QK == 2;  // word from h bits 18..29 (qf_bucket)
-      constexpr bool K3 = QK == 3 || QK == (int)kQfTwoLevel;  // three bits per gram
-      constexpr bool TWO = QK == (int)kQfTwoLevel;            // pair stage first (stride 4 only)
-      static_assert(!TWO || QS == 4, "the two-level probe runs at stride 4");
-      // (the 24-bit multiplies ignore bits 24..31 of f: no mask)
-      auto probe = [&](uint32_t g) __attribute__((always_inline)) -> Probe {
-        const uint32_t gf = g | fold;
-        const uint32_t f = K3 ? gf ^ bfe_u32(gf, 13, 11) : gf;
-        Probe r;
-        r.h = mul_u24(f, 0x9E3779u);
-        if (QQ == 4) r.h = mad_u24(gf >> 8, 0x7F4A7Du, r.h);  // + bytes 1..3 * C2
-        r.p = K3 ? mul_hi_u24(f, 0xC2B2AEu) : 0u;  // K = 2: both bits from h (qf_bits)
-        r.m = K3 ? mul_u24(f, 0x5BD1E9u) : 0u;
-        r.a = TWO ? (((r.h >> 21) << 2) + kQfPairWords * 4u)  // the Bloom half, 11-bit word
-              : kMidIdx ? ((r.h >> 16) & ((kQfWords - 1u) << 2)) : ((r.h >> (32 - kQfBucketBits)) << 2);
-        return r;
-      };
-      auto word = [&](const Probe& r) __attribute__((always_inline)) -> uint32_t {
-        return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_qf) + r.a);
-      };
-      auto test = [&](uint32_t w, const Probe& r) __attribute__((always_inline)) -> uint32_t {
-        uint32_t t = K3 ? (w >> ((r.m >> 24) & 31u)) & (w >> (r.p & 31u))
-                        : shr_byte1(w, r.h) & (w >> ((r.h >> 16) & 31u));
-        if (K3) t &= w >> ((r.h >> 16) & 31u);
-        if (TWO) t &= shr_byte1(w, r.m);  // the fourth bit: m bits 8..12 (qf_bits)
-        return t;
-      };
-      auto hbits = [&](uint32_t g) __attribute__((always_inline)) -> uint32_t {
-        const Probe r = probe(g);
-        return test(word(r), r);
-      };
-      // the samples of chunk c (16 B) -> their grams, in order (QS = 8: dwords 0 and 2;
-      // QS = 6: the grid's bytes 0, 6 and 12, qf_sampled)
-      auto chunk_grams = [&](uint32_t c, auto&& f) __attribute__((always_inline)) {
-        const uint32_t o0 = my0 + 16u * c;
-        const uint4 x = *reinterpret_cast<const uint4*>(s_tile + o0);
-        if constexpr (QS == 6) {
-          f(x.x, 0);
-          f(__builtin_amdgcn_alignbyte(x.z, x.y, 2u), 6);
-          f(x.w, 12);
-          return;
-        }
-        const uint32_t w4 = QS < 4 ? s32[(o0 >> 2) + 4] : 0u;
-        const uint32_t w[5] = {x.x, x.y, x.z, x.w, w4};
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-          for (int o = 0; o < 4; o += (QS < 4 ? QS : 4)) {
-            if ((4 * d + o) % QS != 0) continue;
-            f(o == 0 ? w[d] : __builtin_amdgcn_alignbyte(w[d + 1], w[d], o), 4 * d + o);
-          }
-      };
-      // fast pass: one OR-accumulated bit per chunk (no positions); most tiles stop here
-      uint32_t chit = 0;
-      const uint32_t rot = ((uint32_t)lane >> 1) & 7u;
-      uint32_t hq0 = 0, hq1 = 0, hq2 = 0, hq3 = 0;
-      uint32_t xh = 0xFFFFFFFFu;  // a hit at this tile offset (the compacted stage 2), beside hq
-      if (TWO) {
-        // stage 1: the exact set of the probed grams' low two bytes (pair words [0, 2048)):
-        // sv bit i = the sample at my0 + 4i passes (each chunk's four dwords, two chunks per
-        // step with their eight word reads in flight).  The raw bytes probe: for a folded set
-        // the host lists every case variant of a pair (p with p | 0x2020 in the set), so the
-        // stage has no fold OR and the word's bit is the sample's own low five bits.  Step v
-        // puts chunk (v + rot) & 7 at bits 4v.. (constant shifts); one rotate at the end
-        uint32_t sv = 0;
-#pragma unroll
-        for (int v = 0; v < (ABL(4) ? 0 : 8); v += 2) {
-          const uint32_t ca = ((uint32_t)v + rot) & 7u, cb = ((uint32_t)v + 1u + rot) & 7u;
-          const uint4 xa = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * ca);
-          const uint4 xb = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * cb);
-          const uint32_t g[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-          uint32_t w[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            w[k] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_qf) +
-                                                      ((KLF_PAIR_SWZ ? bfe_u32(g[k], 5, 11) ^ (g[k] & 31u) : bfe_u32(g[k], 5, 11)) << 2));
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            sv |= __builtin_amdgcn_ubfe(w[k], g[k], 1u) << (4 * v + k);  // bit g mod 32 (v_bfe_u32 reads offset[4:0])
-        }
-        sv = __builtin_amdgcn_alignbit(sv, sv, 32u - 4u * rot);  // rotate left by 4 rot (shift mod 32): chunk c at bits 4c..
-        // samples at or past the tile's end (4i >= nvalid) do not count
-        sv &= nvalid >= kLaneBytes ? ~0u : ((1u << ((uint32_t)(nvalid + 3) >> 2)) - 1u);
-        // stage 2: the survivors' 3-bit probe into the Bloom half.  The ~1.4 % survivors
-        // (~30 per tile) are compacted over the wave first, so that one round of 64 lanes
-        // probes them all (each lane's own walk took as many dependent LDS round trips as
-        // the busiest lane had survivors); a hit's tile offset goes to xh.  Past 64
-        // survivors each lane walks its own: a hit's byte position 4i -> its 32-B group
-        // q = i / 8, bit 4i mod 32
-        if (ABL(16)) sv = 0u;  // (KLF_ABL 16: no stage 2)
-        const uint32_t scnt = (uint32_t)__popc(sv);
-        const uint32_t sincl = wave_incl_scan_add(scnt, lane);
-        const uint32_t stot = (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
-        // (the list: the last 32 words of the wave's slot list, free unless more than
-        // kSlotStride - 32 lines start in the tile; a 512-B LDS array of its own cost a third
-        // of the workgroups: 7.7 -> 10.4 ms)
-        if (stot <= 64u && nlines <= (uint32_t)kSlotStride - 32u) {
-          if (stot) {
-            uint16_t* sl = reinterpret_cast<uint16_t*>(s_list + kSlotStride - 32);
-            uint32_t k = sincl - scnt;
-            for (uint32_t m = sv; m; m &= m - 1u) sl[k++] = (uint16_t)(((uint32_t)lane << 5) | (uint32_t)__builtin_ctz(m));
-            wave_lds_sync();
-            if ((uint32_t)lane < stot) {
-              const uint32_t e = sl[lane];  // sample e & 31 of lane e >> 5: tile offset 4 e
-              if (hbits(s32[e]) & 1u) xh = 4u * e;
-            }
-            wave_lds_sync();  // (the next tile rewrites the list)
-          }
-        } else {
-          for (uint32_t m = sv; m; m &= m - 1u) {
-            const uint32_t i = (uint32_t)__builtin_ctz(m);
-            if (hbits(s32[(my0 >> 2) + i]) & 1u) {
-              const uint32_t q = i >> 3, b = 1u << ((4u * i) & 31u);
-              hq0 |= q == 0 ? b : 0u;
-              hq1 |= q == 1 ? b : 0u;
-              hq2 |= q == 2 ? b : 0u;
-              hq3 |= q == 3 ? b : 0u;
-            }
-          }
-        }
-      } else if (QS == 4 || QS == 6) {
-        // stride 4: a chunk's samples are its four dwords (the grid: bytes 0, 6, 12).  Two
-        // chunks per step, their bitmap reads issued before the first test (one LDS round
-        // trip per step, not one per probe)
-        constexpr int kPer = QS == 4 ? 4 : 3;
-#pragma unroll
-        for (int v = 0; v < (ABL(4) ? 0 : 8); v += 2) {
-          const uint32_t ca = ((uint32_t)v + rot) & 7u, cb = ((uint32_t)v + 1u + rot) & 7u;
-          const uint4 xa = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * ca);
-          const uint4 xb = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * cb);
-          uint32_t g[2 * kPer];
-          if constexpr (QS == 4) {
-            g[0] = xa.x; g[1] = xa.y; g[2] = xa.z; g[3] = xa.w;
-            g[4] = xb.x; g[5] = xb.y; g[6] = xb.z; g[7] = xb.w;
-          } else {
-            g[0] = xa.x; g[1] = __builtin_amdgcn_alignbyte(xa.z, xa.y, 2u); g[2] = xa.w;
-            g[3] = xb.x; g[4] = __builtin_amdgcn_alignbyte(xb.z, xb.y, 2u); g[5] = xb.w;
-          }
-          Probe r[2 * kPer];
-          uint32_t w[2 * kPer];
-#pragma unroll
-          for (int k = 0; k < 2 * kPer; ++k) r[k] = probe(g[k]);
-#pragma unroll
-          for (int k = 0; k < 2 * kPer; ++k) w[k] = word(r[k]);
-          uint32_t acc_a = 0, acc_b = 0;
-#pragma unroll
-          for (int k = 0; k < 2 * kPer; ++k) {
-            const uint32_t t = test(w[k], r[k]);
-            if (k < kPer) acc_a |= t; else acc_b |= t;
-          }
-          chit |= ((acc_a & 1u) << ca) | ((acc_b & 1u) << cb);
-        }
-      } else {
-#pragma unroll
-        for (int v = 0; v < (ABL(4) ? 0 : 8); ++v) {
-          const uint32_t c = ((uint32_t)v + rot) & 7u;
-          uint32_t acc = 0;
-          chunk_grams(c, [&](uint32_t g, int) __attribute__((always_inline)) { acc |= hbits(g); });
-          chit |= (acc & 1u) << c;
-        }
-      }
-      // chunks with a possible hit: the sample positions (past the tile's end clipped)
-      if (!TWO && __any(chit != 0)) {
-        for (uint32_t m = chit; m; m &= m - 1u) {
-          const uint32_t c = (uint32_t)__builtin_ctz(m);
-          uint32_t hm = 0;
-          chunk_grams(c, [&](uint32_t g, int pos) __attribute__((always_inline)) { hm |= (hbits(g) & 1u) << pos; });
-          hm = clip(hm, c) << ((c & 1u) * 16u);
-          const uint32_t q = c >> 1;
-          hq0 |= q == 0 ? hm : 0u;
-          hq1 |= q == 1 ? hm : 0u;
-          hq2 |= q == 2 ? hm : 0u;
-          hq3 |= q == 3 ? hm : 0u;
-        }
-      }
-      // short needles: every anchor byte whose dword passes a pre-check is a hit (its
-      // bucket entries name the anchor's offset in the needle); anchors are rare
-      if (ANC && __any(anc != 0)) {
-        const uint32_t npre = a.pats.qf_anc_n;
-        for (uint32_t cm = anc; cm; cm &= cm - 1u) {
-          const uint32_t c = (uint32_t)__builtin_ctz(cm);
-          const uint4 x = *reinterpret_cast<const uint4*>(s_tile + my0 + 16u * c);
-          uint32_t am = 0;
-          for (uint32_t e = clip(eq_mask16(afold ? or4(x, afold) : x, pat), c); e; e &= e - 1u) {
-            const uint32_t pos = my0 + 16u * c + (uint32_t)__builtin_ctz(e);
-            const uint32_t w = __builtin_amdgcn_alignbyte(s32[(pos >> 2) + 1], s32[pos >> 2], pos & 3u) | fold;
-            bool ok = false;
-            for (uint32_t j = 0; j < npre; ++j) ok |= (w & a.pats.qf_anc_pre[2 * j + 1]) == a.pats.qf_anc_pre[2 * j];
-            am |= ok ? 1u << (pos & 15u) : 0u;
-          }
-          am <<= (c & 1u) * 16u;
-          const uint32_t q = c >> 1;
-          hq0 |= q == 0 ? am : 0u;
-          hq1 |= q == 1 ? am : 0u;
-          hq2 |= q == 2 ? am : 0u;
-          hq3 |= q == 3 ? am : 0u;
-        }
-      }
-      if (ABL(8)) {  // timing build: probes only
-        asm volatile("" ::"v"(hq0 | hq1 | hq2 | hq3 | xh));
-        hq0 = hq1 = hq2 = hq3 = 0;
-        xh = 0xFFFFFFFFu;
+    if constexpr (GEN) {
+      uint32_t hq[4] = {0u, 0u, 0u, 0u}, xh = kNoHit;
+      const QProbe<QS, QK, QQ> probe{s_qf, s_tile, a.pats.qf_fold};
+      probe.run(c, s_list, tl.nlines, hq, xh);
+      if (ANC && __any(any.anc != 0)) anchored_hits(a.pats, s_tile, c, any.anc, pat, afold, hq);
+      if (ABL(c, 8)) {  // timing build: probes only
+        asm volatile("" ::"v"(hq[0] | hq[1] | hq[2] | hq[3] | xh));
+        hq[0] = hq[1] = hq[2] = hq[3] = 0;
+        xh = kNoHit;
       }
       // (the count only where some lane has a hit: ~1.5 % of C5's tiles)
-      if (__any((hq0 | hq1 | hq2 | hq3) != 0u || xh != 0xFFFFFFFFu) && (!abl || (KLF_ABL & (65536 | 131072)))) {
-        const uint32_t nh = (uint32_t)(__popc(hq0) + __popc(hq1) + __popc(hq2) + __popc(hq3)) + (xh != 0xFFFFFFFFu ? 1u : 0u);
-        // tile-owned slots (u16 tile offsets, no atomics); only a tile with more than
-        // kHitSlots hits spills the rest to the global list
-        const uint32_t ih = wave_incl_scan_add(nh, lane);
-        const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)ih, 63);
-        uint32_t ob = 0;
-        if (tot > kHitSlots) {
-          if (lane == 63) ob = atomicAdd(&a.counters[kCtrHits], tot - kHitSlots);
-          ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, 63);
-        }
-        uint16_t* hs = a.hslots + (size_t)tile * kHitSlots;
-        // one or two hits of a tile that keeps no line slot in its TileStat go to its
-        // pool_base halves (KLF_HIT_INLINE): no 2-B stores into a half-written 64-B slot line
-        // (C4: ~1.4 M tiles with hits per step)
-        hinl = KLF_HIT_INLINE && tot <= 2u && !dense && nlines != 1u;
-        uint16_t* hd = hinl ? reinterpret_cast<uint16_t*>(s_h2[GEN ? wv : 0]) : hs;
-        uint32_t k = ih - nh;
-        if (xh != 0xFFFFFFFFu) {
-          if (k < kHitSlots) {
-            hd[k] = (uint16_t)xh;
-          } else if ((uint64_t)ob + (k - kHitSlots) < a.qhits_cap) {
-            a.qhits[ob + (k - kHitSlots)] = sd.base + (uint64_t)rel_lo + xh;
-          } else {
-            atomicOr(&a.counters[kCtrHitsOver], 1u);
-          }
-          ++k;
-        }
-        const uint32_t hq[4] = {hq0, hq1, hq2, hq3};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          for (uint32_t m = hq[q]; m; m &= m - 1u, ++k) {
-            const uint32_t off = my0 + 32u * q + (uint32_t)__builtin_ctz(m);
-            if (k < kHitSlots) {
-              hd[k] = (uint16_t)off;
-            } else if ((uint64_t)ob + (k - kHitSlots) < a.qhits_cap) {
-              a.qhits[ob + (k - kHitSlots)] = sd.base + (uint64_t)rel_lo + off;
-            } else {
-              atomicOr(&a.counters[kCtrHitsOver], 1u);
-            }
-          }
-        tile_hits = tot < kHitSlots ? tot : kHitSlots;
-        if (hinl) {
-          wave_lds_sync();
-          const uint32_t h2 = s_h2[GEN ? wv : 0][0];  // (hit 0 in the low half, hit 1 in the high)
-          hit2 = tot > 1u ? h2 : (h2 & 0xFFFFu);
-        }
-      }
+      if (__any((hq[0] | hq[1] | hq[2] | hq[3]) != 0u || xh != kNoHit) && (!abl || (KLF_ABL & (65536 | 131072))))
+        tile_hits = emit_hits(a, c, hq, xh);
     }
 
-    // ---- per-tile record: the first 64 slots and the TileStat, two store instructions
-    // on every path (see the loop entry) ----
-#if KLF_SCAN_PACKSUM
-    // one reduction for both counts (each <= 8,193 per tile: 16 bits apiece, no carry from
-    // the low half) and a ballot for the deferred lines, whose count nothing reads
-    // (at most one line per lane -- 64 lines or fewer: two ballots' popcounts)
-    const uint32_t pq = (KLF_SCAN_BALLOT && nlines <= 64u)
-                            ? (uint32_t)__popcll(__ballot(n_parsed != 0u)) | ((uint32_t)__popcll(__ballot(n_since != 0u)) << 16)
-                            : wave_sum(n_parsed | (n_since << 16));
-    const uint32_t pp = pq & 0xFFFFu, qq = pq >> 16;
-    const uint32_t dd = __any(n_defer != 0) ? 1u : 0u;
-#elif KLF_SCAN_SUMSKIP  // A/B: no reductions on tiles where no line starts (wave-uniform)
-    uint32_t pp = 0, qq = 0, dd = 0;
-    if (nlines) { pp = wave_sum(n_parsed); qq = wave_sum(n_since); dd = wave_sum(n_defer); }
-#else
-    const uint32_t pp = wave_sum(n_parsed), qq = wave_sum(n_since), dd = wave_sum(n_defer);
-#endif
-    any_defer |= dd != 0;
-    {
-      // A tile's line slots: one line start -> the slot in its TileStat (kTsInline); two or
-      // more -> appended to the wave's own chunk of the pool (RunArgs::wave_pool, round 6: a
-      // sequential stream of whole lines per wave, where the 1,152-B-stride record regions
-      // took a 128-B store per tile however few its slots), 16-B aligned, TileStat bit 0 and
-      // pool_base as for a dense tile (whose slots the line list wrote to the pool itself).
-      // 16 B per lane: narrower per-lane stores cost several times more per byte.
-      const bool inl = KLF_TS_INLINE && !dense && nlines == 1u;
-      const bool pooled = a.wave_pool && !dense && nlines >= 2u;
-      // (timing builds: KLF_ABL 65536 drops only the slot stores, 131072 only the TileStat stores)
-      const bool no_slots = (abl && !(KLF_ABL & (65536 | 131072))) || ABL(65536);
-      uint32_t pb = dense ? pool_base : 0u, nunits = 0;
-      uint32_t* sdst = trec;  // the record region (a.wave_pool == 0: unit 0 the TileStat copy)
-      if (pooled && !no_slots) {
-        // 16-B granules; a run of 16 slots or more starts on a 128-B line and fills whole
-        // lines (a run straddling lines left partly written lines behind: C3 +1.6 %, r6f)
-        const bool whole = nlines > 12u;
-        const uint32_t need = whole ? (nlines + 31u) & ~31u : (nlines + 3u) & ~3u;
-        if (whole) wp_cur = (wp_cur + 31u) & ~31u;  // (chunks start 128-B aligned: see below)
-        if (wp_cur + need > wp_end) {  // (wave-uniform) a new chunk
-          const uint32_t ch = need > a.pool_chunk ? need : a.pool_chunk;
-          uint32_t b = 0;
-          if (lane == 0) b = atomicAdd(&a.counters[kCtrPool], ch);
-          b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
-          wp_cur = b;
-          wp_end = (uint64_t)b + ch <= a.pool_cap ? b + ch : b;  // (past the pool: no room, the run is redone)
-          if (wp_end == b && lane == 0) atomicOr(err_flag, 1u);
-        }
-        if (wp_cur + need <= wp_end) {
-          pb = wp_cur;
-          wp_cur += need;
-          nunits = need / 4u;
-          sdst = a.pool + pb;
-        }
-      } else if (!a.wave_pool && !no_slots && !dense && nlines > 1u - (KLF_TS_INLINE ? 0u : 1u)) {
-        nunits = ((kRecHead + nlines + 31u) & ~31u) / 4u;  // the record region (whole 128-B lines)
-      }
-      const uint32_t w0 = agg, w1 = (dense || pooled) ? pb : (inl ? s_list[0] : (hinl ? hit2 : 0u));
-      const uint32_t w2 = (pp & 0xFFFFu) | (qq << 16);
-      const bool hh = LIT && __any(n_hit != 0);  // some line starting here holds the literal
-      const uint32_t w3 = (((dense || (pooled && nunits)) ? 1u : 0u) | (carry ? 2u : 0u) | (dd ? 4u : 0u) | (hh ? 8u : 0u) |
-                           (inl ? kTsInline : 0u) | (hinl ? kTsHitInline : 0u)) |
-                          ((uint32_t)(uint16_t)(GEN ? tile_hits : carry) << 16);  // GEN: hit slots used
-      const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(sdst, 0, (int)(nunits * 16u), 0x00020000);
-      typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-      const uint32_t ushift = a.wave_pool ? 0u : 1u;  // (the record region: unit 0 the TileStat)
-      for (uint32_t u = (uint32_t)lane; u < (nunits > 64u ? 128u : 64u); u += 64) {  // one or two stores
-        const uint32_t us = u - ushift;  // (u = 0 of a record: -1)
-        const uint32_t li = u < ushift ? 0u : (4u * us < (uint32_t)kSlotStride - 4u ? 4u * us : (uint32_t)kSlotStride - 4u);
-        const uint4 sl = *reinterpret_cast<const uint4*>(s_list + li);
-        const u32x4v v = u >= ushift ? u32x4v{sl.x, sl.y, sl.z, sl.w} : u32x4v{w0, w1, w2, w3};
-        __builtin_amdgcn_raw_buffer_store_b128(v, rrs, 16u * u, 0, 0);
-      }
-      // the group's TileStats, one 128-B store at its last tile (lanes past it dropped)
-      const uint32_t gk = tile % kScanGroup, g0 = tile - gk;
-      if (GEN) {
-        if ((uint32_t)lane == gk) stv = make_uint4(w0, w1, w2, w3);
-      } else {
-        if (lane == 0) s_gstat[wv][gk] = make_uint4(w0, w1, w2, w3);
-        wave_lds_sync();
-      }
-      const bool gend = gk == kScanGroup - 1 || tile + 1 >= a.ntiles;
-      const uint32_t ng = a.ntiles - g0 < kScanGroup ? a.ntiles - g0 : kScanGroup;
-      const __amdgpu_buffer_rsrc_t srs =
-          __builtin_amdgcn_make_buffer_rsrc(a.tstat + g0, 0, (gend && (!abl || (KLF_ABL & 65536))) && !ABL(131072) ? (int)(16u * ng) : 0, 0x00020000);
-      const uint4 gs = GEN ? stv : s_gstat[GEN ? 0 : wv][lane & (kScanGroup - 1)];
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4v{gs.x, gs.y, gs.z, gs.w}, srs, 16u * (uint32_t)lane, 0, 0);
-    }
-    asm volatile("" ::: "memory");  // the next stage overwrites the LDS region read above
+    TileTotals tt;
+    tt.pq = packed_counts(n, tl.nlines);
+    tt.defer = __any(n.defer != 0);
+    tt.hit = LIT && __any(n.hits != 0);  // some line starting here holds the literal
+    tt.carry = n.carry;
+    tt.tile_hits = tile_hits;
+    any_defer |= tt.defer;
+    store_record<MODE>(a, c, tl, ev.agg, tt, s_list, wp, stv, s_gstat[GEN ? 0 : wv]);
+    asm volatile("" ::: "memory");  // the next stage overwrites the LDS region read above; stays at the loop's end
   }
   if (any_defer && lane == 0 && !abl) a.counters[kCtrDefer] = 1u;
-  if (FUSE && range_t0 < tile_end) {  // the range's last extent and the state it leaves
-    fz_close();
-    if (lane == 0) {
-      uint64_t* ri = a.fuse_rinfo + 4 * (size_t)gw;
-      ri[0] = fz_res;
-      ri[1] = (fz_known ? 1u : 0u) | (fz_sel ? 2u : 0u);
-      ri[2] = (uint64_t)(int64_t)fz_crel;
-      ri[3] = fz_part;
-    }
-  }
+  if (FUSE && range_t0 < tile_end) fz.finish(a, gw, lane);
   if (KLF_ABL != 0 && lane == 0) atomicAdd(&g_abl_waves, 1u);
-#undef ABL
 }
+#undef ABL
 
 // ---- K1e: general parse of the deferred lines (non-canonical timestamp shapes) ---------
 // One wave per tile that reported deferred lines: Go time.Parse(RFC3339Nano) restated
@@ -1718,17 +1820,10 @@ __global__ __launch_bounds__(256, KLF_TINDEX_WAVES) void k_tindex(RunArgs a) {
     }
 #pragma unroll
     for (int u = 0; u < FB; ++u) {
-      // {tile, its hit's tile offset << 32}: inline hits from the TileStat (L2: this kernel
-      // just read it), the others from the tile's hit slots
+      // {tile, its hit's tile offset << 32}, from the tile's hit slots
       off[u] = 0;
       if (ftile[u] == ~0u) continue;
-      if (KLF_HIT_INLINE) {
-        const TileStat& tsh = a.tstat[ftile[u]];
-        off[u] = (tsh.flags & kTsHitInline) ? ((tsh.pool_base >> (16u * fj[u])) & 0xFFFFu)
-                                            : (uint32_t)a.hslots[(size_t)ftile[u] * kHitSlots + fj[u]];
-      } else {
-        off[u] = a.hslots[(size_t)ftile[u] * kHitSlots + fj[u]];
-      }
+      off[u] = a.hslots[(size_t)ftile[u] * kHitSlots + fj[u]];
     }
 #pragma unroll
     for (int u = 0; u < FB; ++u)
@@ -5087,15 +5182,24 @@ hipError_t launch_gen_q(const RunArgs& a, hipStream_t st, int num_cus) {
   if constexpr (QS == 4)
     if (a.pats.qf_k == kQfTwoLevel)  // the two-level probe (stride 4, no anchor)
       return launch_scan<kScanGen, 4, (int)kQfTwoLevel, QQ>(a, st, num_cus);
-  if (QS == 8 && a.pats.qf_anc_on)  // short needles anchored (only beside stride-8 probes)
-    return a.pats.qf_k == 2 ? launch_scan<kScanGen, QS, 2, QQ, true>(a, st, num_cus)
-                            : launch_scan<kScanGen, QS, 3, QQ, true>(a, st, num_cus);
+  // short needles anchored: only beside stride-8 probes (choose_layout anchors at the long
+  // needles' stride, and those are 10 bytes or longer), so no other stride has the variant
+  if constexpr (QS == 8)
+    if (a.pats.qf_anc_on)
+      return a.pats.qf_k == 2 ? launch_scan<kScanGen, QS, 2, QQ, true>(a, st, num_cus)
+                              : launch_scan<kScanGen, QS, 3, QQ, true>(a, st, num_cus);
+  if (a.pats.qf_anc_on) return hipErrorInvalidValue;  // (an anchored layout at another stride: no such scan)
   return a.pats.qf_k == 2 ? launch_scan<kScanGen, QS, 2, QQ>(a, st, num_cus)
                           : launch_scan<kScanGen, QS, 3, QQ>(a, st, num_cus);
 }
 template <int QS>
 hipError_t launch_gen(const RunArgs& a, hipStream_t st, int num_cus) {
-  return a.pats.qf_w24 ? launch_gen_q<QS, 4>(a, st, num_cus) : launch_gen_q<QS, 3>(a, st, num_cus);
+  // stride 1 is the stride of a 3-byte shortest needle, whose grams are 3 bytes (stride_rule):
+  // there is no stride-1 scan over 4-byte grams
+  if constexpr (QS == 1)
+    return a.pats.qf_w24 ? hipErrorInvalidValue : launch_gen_q<1, 3>(a, st, num_cus);
+  else
+    return a.pats.qf_w24 ? launch_gen_q<QS, 4>(a, st, num_cus) : launch_gen_q<QS, 3>(a, st, num_cus);
 }
 
 static hipError_t launch_tail_stage(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int num_cus, uint32_t& m);

@@ -96,16 +96,11 @@ constexpr uint32_t kQfTwoLevel = 5;
 constexpr uint32_t kQfPairWords = 2048;
 // The pair set's word of pair p (bit p & 31): p >> 5.  Its bank bits are the first byte's
 // top three bits and the second byte's low two: on ASCII text about a dozen of the 32 banks,
-// ~2x the LDS-active cycles in bank conflicts (C4, pmc_c4).  KLF_PAIR_SWZ=1 folds p's low
-// five bits into them (all 32 banks) for one more VALU per sample: C4 k_scan 7.60 -> 7.97 ms
-// (same box, two rounds, gpurun_out/r5k) -- the pair stage is bound by its instructions, not
-// by the conflicts.
-#ifndef KLF_PAIR_SWZ
-#define KLF_PAIR_SWZ 0
-#endif
-__host__ __device__ inline uint32_t qf_pair_word(uint32_t p) {
-  return KLF_PAIR_SWZ ? (((p >> 5) ^ (p & 31u)) & (kQfPairWords - 1u)) : ((p >> 5) & (kQfPairWords - 1u));
-}
+// ~2x the LDS-active cycles in bank conflicts (C4, pmc_c4).  Folding p's low five bits into
+// them (all 32 banks) for one more VALU per sample measured slower, C4 k_scan 7.60 -> 7.97 ms
+// (same box, two rounds; the variant is in the history): the pair stage is bound by its
+// instructions, not by the conflicts.
+__host__ __device__ inline uint32_t qf_pair_word(uint32_t p) { return (p >> 5) & (kQfPairWords - 1u); }
 __host__ __device__ inline bool qf_k3(uint32_t k) { return k == 3 || k == kQfTwoLevel; }
 __host__ __device__ inline uint32_t qf_f(uint32_t g, uint32_t k) {
   const uint32_t g24 = g & 0xFFFFFFu;

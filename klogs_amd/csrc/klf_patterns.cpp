@@ -1568,7 +1568,7 @@ void place_needles(CompiledSet& out, const DataStats* st) {
         cost = 1e6 * qf_samples_per_tile(c.qf_stride) / 8192.0 + (c.qf_anc_on ? c.qf_anc_share * 1e3 : 0.0);
       }
       char buf[64];
-      snprintf(buf, sizeof buf, " [est %.0f VALU/tile]", cost);
+      snprintf(buf, sizeof buf, " k=%u [est %.0f VALU/tile]", c.qf_k, cost);  // (k: bits per gram, 5 = two-level)
       c.qf_layout += buf;
       if (getenv("KLF_DIAG"))
         fprintf(stderr, "[klf] layout candidate (variant %u): %s (tables %.0f us, cost %.0f us)\n", v, c.qf_layout.c_str(),

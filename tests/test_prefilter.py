@@ -7,6 +7,7 @@ import random
 import pytest
 
 import klf_oracle as po
+import scan_variants as sv
 from klogs_amd import engine as E
 from klogs_amd import synth
 
@@ -114,6 +115,50 @@ def test_prefilter_off_falls_back(grep, match, why):
 def test_gram_and_stride_choice(grep, match, q, stride):
     _, info = E.debug_prefilter(b"", grep=grep, match=match)
     assert info["on"] and (info["q"], info["stride"]) == (q, stride), info
+
+
+@pytest.mark.parametrize("tuned", [False, True])
+@pytest.mark.parametrize("grep,match", [
+    ([b"abc", b"0123456789"], []),
+    (sv.needles(40, 3, 5), []),
+    ([b"xyz", b"qrs", b"a longer needle"], []),
+    ([b"abc"] + sv.needles(1600, 5, 6), []),
+    ([b"0123456789AB"], [rb"\d+abc\d+"]),  # (the regex's factor is the 3-byte needle)
+])
+def test_three_byte_needle_means_stride_1_and_3_byte_grams(grep, match, tuned, monkeypatch):
+    """A shortest needle of 3 bytes gives stride 1 and q = min(4, 3 - 1 + 1) = 3, placed from
+    the data's statistics (tuned) or without them (KLF_QF_TUNE=0): there is no stride-1 scan
+    over 4-byte grams (launch_gen<1> rejects one)."""
+    monkeypatch.delenv("KLF_QF_QMAX", raising=False)
+    monkeypatch.delenv("KLF_QF_ANCHOR", raising=False)
+    if not tuned:
+        monkeypatch.setenv("KLF_QF_TUNE", "0")
+    sample = synth.generate(synth.TEXT, 4, 0, 60_000) if tuned else b""
+    h = E.debug_prefilter_hits(sample, b"", grep=grep, match=match)
+    assert (h["stride"], h["q"]) == (1, 3), h
+
+
+GEN_VARIANTS = [v for v in sv.TABLE if v.mode == "gen"]
+
+
+def test_scan_variant_table_is_complete():
+    """plain, one-pass, literal; two-level x 2 gram lengths; strides 2/4/6/8 x 2 x 2 bit
+    counts; stride 1 x 2; anchored x 2 x 2: every k_scan instantiation."""
+    assert len({(v.mode, v.S, v.q, v.k, v.anchored) for v in sv.TABLE}) == 27
+
+
+@pytest.mark.parametrize("v", GEN_VARIANTS, ids=[v.name for v in GEN_VARIANTS])
+def test_scan_variant_table_layouts(v, monkeypatch):
+    """Each general entry of the table tests/test_gpu_scan_variants.py runs selects the
+    layout it names (stride, gram bytes, bits per gram, anchored)."""
+    for k in ("KLF_QF_TUNE", "KLF_QF_TWO", "KLF_QF_ANCHOR", "KLF_QF_QMAX"):
+        monkeypatch.delenv(k, raising=False)
+    for k, val in v.env.items():
+        monkeypatch.setenv(k, val)
+    data = b"".join(sv.streams(v))
+    h = E.debug_prefilter_hits(b"" if v.env.get("KLF_QF_TUNE") == "0" else data, data[:20000], grep=v.grep)
+    assert (h["stride"], h["q"], h["k"], h["anchor"] is not None) == (v.S, v.q, v.k, v.anchored), h
+    assert f" k={v.k} " in h["layout"], h
 
 
 def test_short_needles_anchored():
