@@ -397,6 +397,75 @@ int klf_timeline_write(klf_timeline* t, int fd, uint64_t* written);
 int klf_timeline_ms(const klf_timeline* t, double* ms);
 void klf_timeline_free(klf_timeline* t);
 
+/* ---- grouped counts (SPEC.md S4e; --top K) ------------------------------------------ */
+/* The most frequent messages of a finished run: sort | uniq -c | sort -rn | head over the set r
+ * was selected from, without copying a line to the host.  For a result r that is the engine's
+ * latest, H is klf_result_histogram's H: the parsed lines of M (a run's result or a klf_retail
+ * of one), G' (klf_regroup), G'' (klf_window), or every parsed line on a run's result of an
+ * engine without patterns; taken before --since and --tail, like klf_counts.matched.  The key of
+ * a line is its S1 content without the terminating '\n' (a '\r' stays), cut to its first max_key
+ * bytes when max_key > 0, then, with KLF_GROUPS_MASK_DIGITS, with every maximal run of ASCII
+ * '0'..'9' replaced by one '#' (truncation first, masking second).  The empty key is a key; a
+ * terminated line and an unterminated fragment with the same content share one.  Each distinct
+ * key is a group: count = its lines in H, first / last = its lowest / highest line in (stream
+ * id, line number) order over all streams.  Groups are ordered by count descending, then first
+ * ascending (a total order); the object holds the first min(top, n_groups) of them, and
+ * klf_groups_totals gives n_groups (distinct keys) and n_lines = |H| = the sum of every group's
+ * count = klf_counts.matched over the streams (klf_counts.parsed on a run's result of an engine
+ * without patterns).  Two lines are in one group iff their keys are byte-equal: hashing only
+ * chooses where the device table is probed.
+ * Read-only like klf_result_histogram: r stays the latest result and stays valid, nothing of it
+ * is written, and the call may be repeated with other options.  Read again: the selection
+ * bitmap (L/8 bytes; the line meta, 2 L, without patterns) and, per line of H, its line-index
+ * entry (built now if the run left it out), its meta and its content bytes in the batch, which
+ * must still be resident (klf_run_device: the caller's buffer).  On an engine without patterns
+ * that is a second full read of the batch.
+ * A klf_groups owns its device and host buffers (the entry records and their key bytes): it
+ * stays valid through later runs and klf_reset until klf_groups_free, which must come before
+ * klf_close.  The hash table and the sort's scratch are freed before klf_result_groups returns.
+ * Host views copy D2H on first access.  klf_groups_entries: entry k's key is key_len bytes at
+ * key_off of klf_groups_keys' bytes.  klf_groups_ms: device time of the call, first launch to
+ * last.
+ * KLF_EINVAL (checked first, without touching the device): null r, o or out; top == 0 or above
+ * KLF_GROUPS_MAX_TOP; max_groups above KLF_GROUPS_MAX_GROUPS (0 means 2^20); unknown flag bits.
+ * KLF_ESTATE: r is not the engine's latest result.  KLF_ETOOBIG: more than max_groups distinct
+ * keys (this depends on the number of distinct keys alone; klf_last_error suggests masking or a
+ * larger max_groups), or 2^40 or more lines in the run.  KLF_ENOMEM: an allocation failed (the
+ * table takes 32 bytes a slot, 2 to 4 slots per max_groups, fewer when the run has fewer lines).  An H with no
+ * line gives a valid empty object (n_groups = 0, no entries).  Not promised: follow sessions (a
+ * flush's groups cover that flush) and shard.run_split.  Replaces nothing in the reference,
+ * whose per-container files (cmd/root.go:341-374) stay as they are. */
+#define KLF_GROUPS_MASK_DIGITS 1u
+#define KLF_GROUPS_MAX_TOP 65536u
+#define KLF_GROUPS_MAX_GROUPS (1u << 26)
+typedef struct klf_groups_opts {   /* 16 bytes */
+  uint32_t top;         /* 1 .. KLF_GROUPS_MAX_TOP: entries returned at most */
+  uint32_t max_groups;  /* distinct keys the call can hold; 0 = 2^20 */
+  uint32_t max_key;     /* key = the first max_key content bytes; 0 = all */
+  uint32_t flags;       /* KLF_GROUPS_* */
+} klf_groups_opts;
+typedef struct klf_group_entry {   /* 48 bytes */
+  uint64_t count;
+  uint64_t first_line, last_line;  /* 0-based in their streams */
+  uint64_t key_off;                /* start in the key bytes */
+  uint32_t first_stream, last_stream;
+  uint32_t key_len, _pad;
+} klf_group_entry;
+typedef struct klf_groups klf_groups;
+int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_groups** out);
+int klf_groups_entries(klf_groups* g, const klf_group_entry** e, uint64_t* n);
+int klf_groups_keys(klf_groups* g, const uint8_t** bytes, uint64_t* len);
+int klf_groups_totals(const klf_groups* g, uint64_t* n_groups, uint64_t* n_lines);
+int klf_groups_ms(const klf_groups* g, double* ms);
+void klf_groups_free(klf_groups* g);
+/* Host helper, no GPU: the S4e key of one content (without its '\n'), by the normaliser the
+ * kernels run (klf_groupkey.hpp).  *n (nullable) = the key's length, whatever cap is; the key is
+ * written only when it fits: a cap below the key's length is KLF_EINVAL with *n set and nothing
+ * written, so a call with cap = 0 sizes the buffer.  out may be null when cap is 0.  KLF_EINVAL
+ * also for a null content with len > 0 and for unknown flag bits. */
+int klf_group_key(const uint8_t* content, size_t len, uint32_t max_key, uint32_t flags,
+                  uint8_t* out, size_t cap, size_t* n);
+
 /* ---- follow mode (-f) -------------------------------------------- */
 /* The reference streams each container until EOF with Follow set (cmd/root.go:217-218,
  * streamLog :312-339, the "ended prematurely" warning :314-318) while the main goroutine

@@ -23,6 +23,7 @@
 #include "../../include/klf.h"
 #include "../../include/klf_debug.h"
 #include "klf_copypool.hpp"
+#include "klf_groupkey.hpp"
 #include "klf_kernels.hpp"
 #include "klf_patterns.hpp"
 #include "klf_ts.hpp"
@@ -2588,6 +2589,249 @@ extern "C" int klf_timeline_ms(const klf_timeline* t, double* ms) {
 }
 
 extern "C" void klf_timeline_free(klf_timeline* t) { delete t; }
+
+// -------------------------------------------------------------- grouped counts ---
+
+// A groups object owns what it returns, like a timeline: the entry records and the key bytes
+// on the device, and their host copies once a view asked for them.
+struct klf_groups {
+  klf_engine* e = nullptr;
+  uint64_t n = 0, key_bytes = 0, n_groups = 0, n_lines = 0;
+  double ms = 0.0;
+  DevBuf d_entries, d_keys;
+  bool have_entries = false, have_keys = false;
+  std::vector<klf_group_entry> entries;
+  std::vector<uint8_t> keys;
+  ~klf_groups() {
+    d_entries.release();
+    d_keys.release();
+  }
+};
+static_assert(sizeof(klf_group_entry) == sizeof(klf::GrEntry) && sizeof(klf_group_entry) == 48 &&
+                  sizeof(klf_groups_opts) == 16,
+              "klf_group_entry is the kernels' GrEntry");
+static_assert(KLF_GROUPS_MASK_DIGITS == klf::kGroupsMaskDigits, "one flag value for the host helper and the kernels");
+
+namespace {
+// The call's scratch: the hash table, the occupied-slot sums, the sort's items, the slot of each
+// item, the histograms, the block counts, the key lengths, the segment -> stream table; freed
+// when klf_result_groups returns.
+struct GrScratch {
+  DevBuf table, bsum, items[2], gslot, dhist, bcnt, klen, segstream;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~GrScratch() {
+    for (DevBuf* b : {&table, &bsum, &items[0], &items[1], &gslot, &dhist, &bcnt, &klen, &segstream}) b->release();
+    for (auto& x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+}  // namespace
+
+static int gr_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
+  const hipError_t h = b.ensure(bytes);
+  if (h == hipSuccess) return KLF_OK;
+  (void)hipGetLastError();
+  if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string("klf_result_groups: alloc ") + what);
+  return hip_err(e, h, what);
+}
+
+// KLF_GROUPS_HASH_BITS (1..64, a test hook: DESIGN.md): the low bits of the hash that are used.
+static uint32_t groups_hash_bits() {
+  const char* s = getenv("KLF_GROUPS_HASH_BITS");
+  if (!s || !*s) return 64;
+  char* end = nullptr;
+  const long v = strtol(s, &end, 10);
+  return (*end || v < 1 || v > 64) ? 64u : (uint32_t)v;
+}
+
+extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_groups** out) {
+  if (!r || !o || !out) return KLF_EINVAL;
+  klf_engine* e = r->e;
+  if (o->top == 0 || o->top > KLF_GROUPS_MAX_TOP)
+    return set_err(e, KLF_EINVAL, "klf_result_groups: top must be 1 .. 65536");
+  if (o->max_groups > KLF_GROUPS_MAX_GROUPS)
+    return set_err(e, KLF_EINVAL, "klf_result_groups: max_groups above 2^26");
+  if (o->flags & ~KLF_GROUPS_MASK_DIGITS) return set_err(e, KLF_EINVAL, "klf_result_groups: unknown flag bits");
+  if (int rc = check_latest(e, r, "klf_result_groups")) return rc;
+  std::unique_ptr<klf_groups> t(new (std::nothrow) klf_groups());
+  if (!t) return KLF_ENOMEM;
+  t->e = e;
+  const uint32_t nsegs = (uint32_t)r->so.size();
+  if (!nsegs) {  // no stream has bytes
+    *out = t.release();
+    return KLF_OK;
+  }
+  if (r->total_lines >> klf::kGrLineBits)
+    return set_err(e, KLF_ETOOBIG, "klf_result_groups: 2^40 or more lines in the run");
+  if (int rc = ensure_index(e)) return rc;
+  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+  hipStream_t st = e->stream;
+  GrScratch sc;
+  klf::GroupArgs g{};
+  g.v = sel_view(r);
+  g.max_key = o->max_key;
+  g.flags = o->flags;
+  g.hash_bits = groups_hash_bits();
+  // P = pow2 >= 2 * the keys the table must hold: max_groups, or the run's lines when fewer
+  const uint64_t max_groups = o->max_groups ? o->max_groups : (1ull << 20);
+  const uint64_t hold = std::min<uint64_t>(max_groups, r->total_lines);
+  g.table_log2 = 6;
+  while ((1ull << g.table_log2) < 2 * hold) ++g.table_log2;  // (<= 27)
+  const uint64_t P = 1ull << g.table_log2;
+  const size_t cblocks = (size_t)((P + klf::kGrCountBlock - 1) / klf::kGrCountBlock);
+  if (int rc = gr_alloc(e, sc.table, (size_t)(4 * P + 2) * 8, "hash table")) return rc;
+  if (int rc = gr_alloc(e, sc.bsum, (cblocks + 1) * 8, "slot sums")) return rc;
+  g.table = sc.table.as<uint64_t>();
+  g.bsum = sc.bsum.as<uint64_t>();
+  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "groups events");
+  auto finish = [&]() -> int {  // the device time, first launch to last
+    HIPCHK(e, hipEventRecord(sc.ev[1], st), "record groups end");
+    HIPCHK(e, hipStreamSynchronize(st), "sync groups");
+    float f = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "groups timing");
+    t->ms = f;
+    return KLF_OK;
+  };
+  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record groups start");
+  // 1. every line of H into the table; the occupied slots -> n_groups
+  HIPCHK(e, klf::launch_gr_insert(g, st, e->num_cus), "launch k_gr_insert");
+  HIPCHK(e, klf::launch_gr_count(g, st), "launch k_gr_count");
+  uint64_t stats[2] = {0, 0}, n_groups = 0;
+  HIPCHK(e, hipMemcpyAsync(stats, g.table + 4 * P, 16, hipMemcpyDeviceToHost, st), "D2H groups totals");
+  HIPCHK(e, hipMemcpyAsync(&n_groups, g.bsum + cblocks, 8, hipMemcpyDeviceToHost, st), "D2H groups count");
+  HIPCHK(e, hipStreamSynchronize(st), "sync groups count");
+  if (stats[1] || n_groups > max_groups)  // (a full table holds P > max_groups keys: the same answer)
+    return set_err(e, KLF_ETOOBIG, "klf_result_groups: more than max_groups = " + std::to_string(max_groups) +
+                                       " distinct keys; mask digits (KLF_GROUPS_MASK_DIGITS), cut the key (max_key) or "
+                                       "raise max_groups");
+  t->n_lines = stats[0];
+  t->n_groups = n_groups;
+  if (!n_groups) {
+    if (int rc = finish()) return rc;
+    *out = t.release();
+    return KLF_OK;
+  }
+  // 2. one item per group, sorted by (count desc, first asc) with the timeline's passes
+  g.n_groups = n_groups;
+  klf::TlArgs tg{};
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = gr_alloc(e, sc.items[k], n_groups * sizeof(klf::TlItem), "sort items")) return rc;
+    tg.items[k] = sc.items[k].as<klf::TlItem>();
+  }
+  if (int rc = gr_alloc(e, sc.gslot, n_groups * 4, "item slots")) return rc;
+  if (int rc = gr_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
+  g.items = tg.items[0];
+  g.gslot = sc.gslot.as<uint32_t>();
+  g.dhist = tg.dhist = sc.dhist.as<uint64_t>();
+  tg.n = n_groups;
+  HIPCHK(e, klf::launch_gr_fill(g, st, e->num_cus), "launch k_gr_fill");
+  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
+  HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
+  HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
+  const size_t nblocks = (size_t)((n_groups + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
+  uint32_t cur = 0;
+  for (uint32_t p = 0; p < klf::kTlDigits; ++p) {
+    bool one_bin = false;
+    for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n_groups;
+    if (one_bin) continue;
+    if (!tg.bcnt) {
+      if (int rc = gr_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
+      tg.bcnt = sc.bcnt.as<uint32_t>();
+    }
+    HIPCHK(e, klf::launch_tl_pass(tg, p, cur, st), "launch radix pass");
+    cur ^= 1u;
+  }
+  // 3. the first `top` groups: key lengths -> offsets, then the records and the key bytes
+  g.top = (uint32_t)std::min<uint64_t>(o->top, n_groups);
+  std::vector<uint32_t> segstream(nsegs, 0u);
+  for (uint32_t id = 0; id < r->n_streams; ++id)
+    if (r->seg_of[id] >= 0) segstream[(size_t)r->seg_of[id]] = id;
+  if (int rc = gr_alloc(e, sc.segstream, (size_t)nsegs * 4, "segment table")) return rc;
+  HIPCHK(e, hipMemcpyAsync(sc.segstream.p, segstream.data(), (size_t)nsegs * 4, hipMemcpyHostToDevice, st), "H2D segment table");
+  g.segstream = sc.segstream.as<uint32_t>();
+  if (int rc = gr_alloc(e, sc.klen, ((size_t)g.top + 1) * 8, "key lengths")) return rc;
+  g.klen = sc.klen.as<uint64_t>();
+  HIPCHK(e, klf::launch_gr_plan(g, tg.items[cur], st), "launch k_gr_plan");
+  uint64_t total = 0;
+  HIPCHK(e, hipMemcpyAsync(&total, g.klen + g.top, 8, hipMemcpyDeviceToHost, st), "D2H key bytes");
+  HIPCHK(e, hipStreamSynchronize(st), "sync key bytes");
+  if (int rc = gr_alloc(e, t->d_entries, (size_t)g.top * sizeof(klf::GrEntry), "entries")) return rc;
+  if (int rc = gr_alloc(e, t->d_keys, total + 16, "key bytes")) return rc;
+  g.entries = t->d_entries.as<klf::GrEntry>();
+  g.keys = t->d_keys.as<uint8_t>();
+  HIPCHK(e, klf::launch_gr_render(g, tg.items[cur], st), "launch k_gr_render");
+  if (int rc = finish()) return rc;
+  t->n = g.top;
+  t->key_bytes = total;
+  *out = t.release();
+  return KLF_OK;
+}
+
+extern "C" int klf_groups_entries(klf_groups* t, const klf_group_entry** ent, uint64_t* n) {
+  if (!t || !ent || !n) return KLF_EINVAL;
+  klf_engine* e = t->e;
+  if (!t->have_entries && t->n) {
+    try { t->entries.resize((size_t)t->n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
+    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+    HIPCHK(e, hipMemcpy(t->entries.data(), t->d_entries.p, (size_t)t->n * sizeof(klf_group_entry), hipMemcpyDeviceToHost),
+           "D2H group entries");
+  }
+  t->have_entries = true;
+  *ent = t->entries.data();
+  *n = t->n;
+  return KLF_OK;
+}
+
+extern "C" int klf_groups_keys(klf_groups* t, const uint8_t** bytes, uint64_t* len) {
+  if (!t || !bytes || !len) return KLF_EINVAL;
+  klf_engine* e = t->e;
+  if (!t->have_keys && t->key_bytes) {
+    try { t->keys.resize((size_t)t->key_bytes); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
+    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+    HIPCHK(e, hipMemcpy(t->keys.data(), t->d_keys.p, (size_t)t->key_bytes, hipMemcpyDeviceToHost), "D2H group keys");
+  }
+  t->have_keys = true;
+  *bytes = t->keys.data();
+  *len = t->key_bytes;
+  return KLF_OK;
+}
+
+extern "C" int klf_groups_totals(const klf_groups* t, uint64_t* n_groups, uint64_t* n_lines) {
+  if (!t) return KLF_EINVAL;
+  if (n_groups) *n_groups = t->n_groups;
+  if (n_lines) *n_lines = t->n_lines;
+  return KLF_OK;
+}
+
+extern "C" int klf_groups_ms(const klf_groups* t, double* ms) {
+  if (!t || !ms) return KLF_EINVAL;
+  *ms = t->ms;
+  return KLF_OK;
+}
+
+extern "C" void klf_groups_free(klf_groups* t) { delete t; }
+
+extern "C" int klf_group_key(const uint8_t* content, size_t len, uint32_t max_key, uint32_t flags, uint8_t* out,
+                             size_t cap, size_t* n) {
+  if (n) *n = 0;
+  if ((!content && len) || (!out && cap) || (flags & ~KLF_GROUPS_MASK_DIGITS)) return KLF_EINVAL;
+  const size_t span = (size_t)klf::group_key_span(len, max_key);
+  size_t need = 0;
+  {
+    klf::GroupKeyNorm nm(flags);
+    uint8_t c;
+    for (size_t i = 0; i < span; ++i) need += nm.step(content[i], c) ? 1 : 0;
+  }
+  if (n) *n = need;
+  if (need > cap) return KLF_EINVAL;
+  klf::GroupKeyNorm nm(flags);
+  size_t k = 0;
+  for (size_t i = 0; i < span; ++i) {
+    uint8_t c;
+    if (nm.step(content[i], c)) out[k++] = c;
+  }
+  return KLF_OK;
+}
 
 extern "C" int klf_result_last_unparsed(klf_result* r, uint32_t id, uint64_t* rank) {
   int rc = check_result(r, id);

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "klf_groupkey.hpp"
 #include "klf_kernels.hpp"
 #include "klf_ts.hpp"
 
@@ -3618,6 +3619,255 @@ __global__ __launch_bounds__(256) void k_tl_copy(TlArgs g, const TlItem* __restr
   }
 }
 
+// ========================================= grouped counts (klf_result_groups, SPEC.md S4e) ==
+// The lines of H grouped by key.  k_gr_insert is the selected-line walk over H, one lane per
+// line: the lane runs the normaliser (klf_groupkey.hpp) over its content, 16 bytes a load, folds
+// the key bytes into a 64-bit hash and probes the open-addressing table from hash & (P - 1).
+// A free slot is claimed with atomicCAS (the word then names this line as the group's
+// representative); a slot whose tag is the lane's is settled by comparing the two keys byte
+// for byte, both normalised on the fly from the batch.  The hash only chooses where to look:
+// groups are exactly the classes of byte-equal keys, for any hash.  The 64 lines of a round
+// often share a group, so neighbouring lanes that found one slot add once (k_hist's ballot of
+// run heads).  A lane that finds no slot in P probes sets the table-full flag and goes on.
+
+// The content bytes a line's key is made from: S1's content without its '\n', cut to max_key.
+struct GrLine {
+  const uint8_t* p;
+  uint64_t n;
+};
+__device__ __forceinline__ GrLine gr_line(const GroupArgs& g, uint64_t l, uint32_t s) {
+  const SegDesc sd = g.v.segs[s];
+  const uint64_t ls = g.v.line_off[l + s], le = g.v.line_off[l + s + 1];
+  const uint8_t* segp = g.v.bytes + sd.base;
+  const uint32_t plen = line_plen(g, g.v.meta[l], segp, ls, le);
+  uint64_t n = le - ls - plen;
+  if (n && !(le == sd.len && g.v.segout[s].frag)) --n;  // the terminating '\n'
+  return {segp + ls + plen, group_key_span(n, g.max_key)};
+}
+// The key bytes of a line, one after the other.  A 16-B load may reach 15 bytes past the span:
+// into the next line, the next stream or the allocation's slack (kAllocSlack), never used.
+struct GrCursor {
+  const uint8_t* p;
+  uint64_t n, pos, lo, hi;
+  GroupKeyNorm nm;
+  __device__ __forceinline__ GrCursor(const GrLine& q, uint32_t flags) : p(q.p), n(q.n), pos(0), lo(0), hi(0), nm(flags) {}
+  __device__ __forceinline__ int next() {  // -1: the key has ended
+    while (pos < n) {
+      const uint32_t k = (uint32_t)pos & 15u;
+      if (k == 0) {
+        typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+        u64x2 x;
+        __builtin_memcpy(&x, p + pos, 16);
+        lo = x.x;
+        hi = x.y;
+      }
+      const uint8_t c = (uint8_t)(k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8)));
+      ++pos;
+      uint8_t out;
+      if (nm.step(c, out)) return (int)out;
+    }
+    return -1;
+  }
+};
+__device__ __forceinline__ uint64_t gr_mix(uint64_t h, uint64_t x) {
+  h = (h ^ x) * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+// The key's hash: 8 key bytes a step, then the key length.
+__device__ __forceinline__ uint64_t gr_hash(const GrLine& q, uint32_t flags) {
+  GrCursor cur(q, flags);
+  uint64_t h = 0x243F6A8885A308D3ull, acc = 0, len = 0;
+  uint32_t na = 0;
+  for (int c; (c = cur.next()) >= 0;) {
+    acc |= (uint64_t)(uint32_t)c << (8 * na);
+    ++len;
+    if (++na == 8) {
+      h = gr_mix(h, acc);
+      acc = 0;
+      na = 0;
+    }
+  }
+  h = gr_mix(gr_mix(h, acc), len);
+  return h ^ (h >> 32);
+}
+__device__ __forceinline__ bool gr_keys_equal(const GrLine& a, const GrLine& b, uint32_t flags) {
+  GrCursor ca(a, flags), cb(b, flags);
+  for (;;) {
+    const int x = ca.next(), y = cb.next();
+    if (x != y) return false;
+    if (x < 0) return true;
+  }
+}
+__device__ __forceinline__ uint64_t* gr_slots(const GroupArgs& g) { return g.table; }
+__device__ __forceinline__ uint64_t* gr_count(const GroupArgs& g) { return g.table + (1ull << g.table_log2); }
+__device__ __forceinline__ uint64_t* gr_nfirst(const GroupArgs& g) { return g.table + (2ull << g.table_log2); }
+__device__ __forceinline__ uint64_t* gr_last(const GroupArgs& g) { return g.table + (3ull << g.table_log2); }
+__device__ __forceinline__ uint64_t* gr_stats(const GroupArgs& g) { return g.table + (4ull << g.table_log2); }
+constexpr uint64_t kGrLineMask = (1ull << kGrLineBits) - 1ull;
+
+// The slot of line l's group (l of segment s), claimed if the key is new; ~0: the table is full.
+__device__ __forceinline__ uint64_t gr_find_slot(const GroupArgs& g, uint64_t l, uint32_t s) {
+  const uint64_t pmask = (1ull << g.table_log2) - 1ull;
+  const GrLine me = gr_line(g, l, s);
+  uint64_t h = gr_hash(me, g.flags);
+  if (g.hash_bits < 64) h &= (1ull << g.hash_bits) - 1ull;
+  const uint64_t tag = h >> kGrLineBits, mine = tag << kGrLineBits | (l + 1);
+  uint64_t* slots = gr_slots(g);
+  uint64_t i = h & pmask;
+  for (uint64_t probe = 0; probe <= pmask; ++probe, i = (i + 1) & pmask) {
+    uint64_t wd = __hip_atomic_load(slots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (wd == 0) {
+      wd = atomicCAS(reinterpret_cast<unsigned long long*>(slots + i), 0ull, (unsigned long long)mine);
+      if (wd == 0) return i;
+    }
+    if (wd >> kGrLineBits != tag) continue;
+    const uint64_t rep = (wd & kGrLineMask) - 1;
+    if (rep >= g.v.cap_lines) continue;  // (never: slot words are written here alone)
+    if (gr_keys_equal(me, gr_line(g, rep, find_seg_by_line(g.v.segout, g.v.nsegs, rep)), g.flags)) return i;
+  }
+  return ~0ull;
+}
+
+__device__ __forceinline__ uint64_t shfl64_up1(uint64_t x) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, 1, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), 1, 64);
+  return (uint64_t)hi << 32 | lo;
+}
+
+__global__ __launch_bounds__(256) void k_gr_insert(GroupArgs g) {
+  __shared__ WalkLds ws;
+  const int t = threadIdx.x, lane = t & 63;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t total = walk_publish(ws, g.v, view_word(g.v, w, L), l0);
+    __syncthreads();
+    if (lane == 0 && total) atomicAdd(reinterpret_cast<unsigned long long*>(gr_stats(g)), (unsigned long long)total);
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
+      const uint64_t line = q.live ? q.l : 0ull;
+      const uint64_t slot = q.live ? gr_find_slot(g, line, q.s) : ~0ull;  // ~0: no line, or no slot for it
+      if (q.live && slot == ~0ull) atomicOr(reinterpret_cast<unsigned long long*>(gr_stats(g) + 1), 1ull);
+      // a run of lanes with one slot: its head adds the run's length, its own line (the run's
+      // lowest) and the run's last line (lines ascend with the lane)
+      const uint64_t prev = shfl64_up1(slot);
+      const bool head = lane == 0 || slot != prev;
+      const uint64_t heads = __ballot(head);
+      const uint64_t after = lane == 63 ? 0ull : heads >> (lane + 1);  // the heads behind this lane
+      const uint32_t run = after ? (uint32_t)__ffsll((long long)after) : 64u - (uint32_t)lane;
+      const uint64_t tail_line = shfl64(line, lane + (int)run - 1);
+      if (head && slot != ~0ull) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(gr_count(g) + slot), (unsigned long long)run);
+        atomicMax(reinterpret_cast<unsigned long long*>(gr_nfirst(g) + slot), (unsigned long long)~line);
+        atomicMax(reinterpret_cast<unsigned long long*>(gr_last(g) + slot), (unsigned long long)tail_line);
+      }
+    });
+  }
+}
+
+// Thread t of block b owns the slots b * kGrCountBlock + 8 t .. + 7.
+__device__ __forceinline__ uint32_t gr_occupied8(const GroupArgs& g, uint64_t j0) {
+  const uint64_t P = 1ull << g.table_log2;
+  uint32_t m = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 8; ++k)
+    if (j0 + k < P && gr_slots(g)[j0 + k]) m |= 1u << k;
+  return m;
+}
+__global__ __launch_bounds__(256) void k_gr_count(GroupArgs g) {
+  __shared__ uint64_t s_w64[4];
+  const uint64_t j0 = (uint64_t)blockIdx.x * kGrCountBlock + 8ull * threadIdx.x;
+  const uint64_t n = block_sum_u64((uint64_t)__popc(gr_occupied8(g, j0)), s_w64);
+  if (threadIdx.x == 0) g.bsum[blockIdx.x] = n;
+}
+// One item per occupied slot, at the block's base + its rank in the block: the sort key is
+// (2^40 - 1 - count) in sec_key's upper 40 bits, then the group's lowest line (40 bits) over
+// sec_key's lower 24 bits and nsec's lower 16, so ascending keys are (count desc, first asc).
+__global__ __launch_bounds__(256) void k_gr_fill(GroupArgs g) {
+  __shared__ uint32_t s_w[4];
+  const uint64_t j0 = (uint64_t)blockIdx.x * kGrCountBlock + 8ull * threadIdx.x;
+  const uint32_t m = gr_occupied8(g, j0), cnt = (uint32_t)__popc(m);
+  uint32_t tot;
+  uint64_t i = g.bsum[blockIdx.x] + block_incl_scan_u32(cnt, s_w, &tot) - cnt;
+  for (uint32_t k = 0; k < 8; ++k) {
+    if (!((m >> k) & 1u)) continue;
+    const uint64_t j = j0 + k;
+    if (i < g.n_groups) {  // (always: n_groups is the scan's total of the same slots)
+      const uint64_t cn = gr_count(g)[j] & kGrLineMask, first = ~gr_nfirst(g)[j] & kGrLineMask;
+      g.items[i] = TlItem{(kGrLineMask - cn) << 24 | first >> 16, (uint32_t)(first & 0xFFFFu), (uint32_t)i};
+      g.gslot[i] = (uint32_t)j;
+    }
+    ++i;
+  }
+}
+
+// What entry i of the result is made from: its slot and its representative line.
+__device__ __forceinline__ bool gr_top_line(const GroupArgs& g, const TlItem& it, uint64_t* slot, GrLine* q) {
+  if (it.ord >= g.n_groups) return false;  // (never: the sort permutes k_gr_fill's items)
+  const uint64_t j = g.gslot[it.ord];
+  if (j >> g.table_log2) return false;
+  const uint64_t rep = (gr_slots(g)[j] & kGrLineMask) - 1;
+  if (rep >= g.v.cap_lines) return false;
+  *slot = j;
+  *q = gr_line(g, rep, find_seg_by_line(g.v.segout, g.v.nsegs, rep));
+  return true;
+}
+// One wave per entry walks the representative's span 64 bytes a step, a byte a lane, by the
+// normaliser's rule (group_key_emits: it needs the previous byte alone): f(emit, key byte, its
+// position in the key) on every lane of every step; returns the key's length.  Byte loads inside
+// the span only.
+template <class F>
+__device__ __forceinline__ uint64_t gr_wave_key(const GrLine& q, uint32_t flags, int lane, F&& f) {
+  uint64_t written = 0;
+  int carry = 0;  // the previous step's last byte was a digit
+  for (uint64_t base = 0; base < q.n; base += 64) {
+    const bool live = base + lane < q.n;
+    const uint8_t c = live ? q.p[base + lane] : (uint8_t)0;
+    const int dig = live && group_key_digit(c) ? 1 : 0;
+    const int up = __shfl_up(dig, 1, 64);
+    uint8_t out = 0;
+    const bool emit = live && group_key_emits(flags, (lane == 0 ? carry : up) != 0, c, out);
+    const uint64_t m = __ballot(emit);
+    f(emit, out, written + (uint64_t)__popcll(m & ((1ull << lane) - 1ull)));
+    written += (uint64_t)__popcll(m);
+    carry = __shfl(dig, 63, 64);
+  }
+  return written;
+}
+__global__ __launch_bounds__(256) void k_gr_plan(GroupArgs g, const TlItem* __restrict__ sorted) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);  // (wave-uniform)
+  if (i >= g.top) return;
+  uint64_t j, len = 0;
+  GrLine q;
+  if (gr_top_line(g, sorted[i], &j, &q)) len = gr_wave_key(q, g.flags, lane, [](bool, uint8_t, uint64_t) {});
+  if (lane == 0) g.klen[i] = len;
+}
+// The entry record (lane 0), then the key bytes by the same walk.
+__global__ __launch_bounds__(256) void k_gr_render(GroupArgs g, const TlItem* __restrict__ sorted) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);  // (wave-uniform)
+  if (i >= g.top) return;
+  const TlItem it = sorted[i];
+  const uint64_t off = g.klen[i], len = g.klen[i + 1] - off;
+  uint64_t j;
+  GrLine q;
+  GrEntry e{};
+  e.key_off = off;
+  if (gr_top_line(g, it, &j, &q)) {
+    const uint64_t first = ((it.sec_key & 0xFFFFFFull) << 16 | (it.nsec & 0xFFFFu)), last = gr_last(g)[j];
+    const uint32_t fs = find_seg_by_line(g.v.segout, g.v.nsegs, first), ls = find_seg_by_line(g.v.segout, g.v.nsegs, last);
+    e.count = kGrLineMask - (it.sec_key >> 24);
+    e.first_line = first - g.v.segout[fs].line_lo;
+    e.last_line = last - g.v.segout[ls].line_lo;
+    e.first_stream = g.segstream[fs];
+    e.last_stream = g.segstream[ls];
+    e.key_len = (uint32_t)len;
+    gr_wave_key(q, g.flags, lane, [&](bool emit, uint8_t c, uint64_t k) {
+      if (emit && k < len) g.keys[off + k] = c;  // (k < len always: the plan walked the same bytes)
+    });
+  }
+  if (lane == 0) g.entries[i] = e;
+}
+
 // Zeroes the run's counters and per-stream records (one launch instead of memsets).
 __global__ __launch_bounds__(256) void k_init(RunArgs a) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -5530,6 +5780,50 @@ hipError_t launch_tl_copy(const TlArgs& g, uint32_t which, hipStream_t st) {
   const uint64_t nb = (g.n + kTlPlanBlock - 1) / kTlPlanBlock;
   if (!nb) return hipSuccess;
   hipLaunchKernelGGL(k_tl_copy, dim3((uint32_t)nb), dim3(256), 0, st, g, g.items[which & 1]);
+  return hipGetLastError();
+}
+
+static uint32_t gr_count_blocks(const GroupArgs& g) {
+  return (uint32_t)(((1ull << g.table_log2) + kGrCountBlock - 1) / kGrCountBlock);
+}
+
+hipError_t launch_gr_insert(const GroupArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.table, 0, ((4ull << g.table_log2) + 2) * 8, st);
+  if (e != hipSuccess || !g.v.nchunks) return e;
+  hipLaunchKernelGGL(k_gr_insert, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_gr_count(const GroupArgs& g, hipStream_t st) {
+  const uint32_t nb = gr_count_blocks(g);
+  hipLaunchKernelGGL(k_gr_count, dim3(nb), dim3(256), 0, st, g);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.bsum, (uint64_t)nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
+  if (e != hipSuccess || !g.n_groups) return e;
+  hipLaunchKernelGGL(k_gr_fill, dim3(gr_count_blocks(g)), dim3(256), 0, st, g);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const uint64_t nb = (g.n_groups + 255) / 256, dmax = (uint64_t)num_cus * 8;
+  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items, g.n_groups, g.dhist);
+  return hipGetLastError();
+}
+
+hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t st) {
+  if (g.top) {
+    hipLaunchKernelGGL(k_gr_plan, dim3((g.top + 3) / 4), dim3(256), 0, st, g, sorted);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.klen, (uint64_t)g.top);
+  return hipGetLastError();
+}
+
+hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_t st) {
+  if (!g.top) return hipSuccess;
+  hipLaunchKernelGGL(k_gr_render, dim3((g.top + 3) / 4), dim3(256), 0, st, g, sorted);
   return hipGetLastError();
 }
 

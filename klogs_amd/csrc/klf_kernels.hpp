@@ -468,6 +468,57 @@ hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t stream);
 // k_tl_copy: g.entries and g.out from the sorted g.items[which] and the scanned g.psum.
 hipError_t launch_tl_copy(const TlArgs& g, uint32_t which, hipStream_t stream);
 
+// Grouped counts of a finished run (klf_result_groups, SPEC.md S4e): the lines of H grouped by
+// their key (klf_groupkey.hpp), the groups ordered by (count desc, first asc).
+//   k_gr_insert               the selected-line walk over H: each line hashes its key and finds its
+//                             group's slot in an open-addressing table (one u64 word per slot: a
+//                             hash tag and the representative line that claimed it; equal tags
+//                             are settled by comparing the two keys byte for byte), then adds to
+//                             the slot's count / lowest line / highest line
+//   k_gr_count / k_tl_scan    occupied slots per kGrCountBlock slots, their prefix -> n_groups
+//   k_gr_fill / k_tl_digits   one TlItem per group: key = (~count, first), 80 bits of the 96
+//   launch_tl_pass            the timeline's stable LSD passes over those items
+//   k_gr_plan / k_tl_scan / k_gr_render   key lengths of the first `top` groups, their prefix,
+//                             then the entry records and the key bytes
+// No kernel waits on another thread: inside k_gr_insert a thread relies on the slot words alone
+// (atomicCAS / agent-scope atomic loads); everything else it reads is immutable during the call.
+struct GrEntry {      // = klf_group_entry
+  uint64_t count, first_line, last_line, key_off;
+  uint32_t first_stream, last_stream, key_len, _pad;
+};
+static_assert(sizeof(GrEntry) == 48, "group records");
+constexpr uint32_t kGrLineBits = 40;        // a slot word: tag << 40 | representative line + 1
+constexpr uint32_t kGrCountBlock = 2048;    // slots per block of the count / fill (8 per thread)
+struct GroupArgs {
+  SelView v;                // bits_in null: the parsed lines (no patterns)
+  uint32_t max_key, flags;  // klf_groups_opts
+  uint32_t hash_bits;       // low bits of the hash that are used (64; KLF_GROUPS_HASH_BITS)
+  uint32_t table_log2;      // P = 1 << table_log2 slots
+  // [4 P + 2] u64, zeroed by launch_gr_insert: the slot words, then per slot the count, ~(its
+  // lowest line) and its highest line (global line indices), then {|H|, table full}
+  uint64_t* table;
+  uint64_t* bsum;           // [P / kGrCountBlock + 1] occupied slots per block, then prefix and n_groups
+  uint64_t n_groups;        // (known after launch_gr_count)
+  TlItem* items;            // [n_groups] the sort's input
+  uint32_t* gslot;          // [n_groups] TlItem::ord -> slot
+  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_gr_fill)
+  uint32_t top;             // groups rendered: min(opts.top, n_groups)
+  uint64_t* klen;           // [top + 1] key lengths, then their prefix and the total
+  const uint32_t* segstream;  // [nsegs] segment -> stream id
+  GrEntry* entries;         // [top]
+  uint8_t* keys;            // the key bytes
+};
+// Zeroes g.table, then k_gr_insert.
+hipError_t launch_gr_insert(const GroupArgs& g, hipStream_t stream, int num_cus);
+// k_gr_count + k_tl_scan: g.bsum[blocks] = n_groups afterwards.
+hipError_t launch_gr_count(const GroupArgs& g, hipStream_t stream);
+// k_gr_fill into g.items / g.gslot, then g.dhist (k_tl_digits).
+hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t stream, int num_cus);
+// k_gr_plan + k_tl_scan over the first g.top of `sorted`: g.klen[g.top] = the key bytes.
+hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t stream);
+// k_gr_render: g.entries and g.keys from `sorted` and the scanned g.klen.
+hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_t stream);
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]

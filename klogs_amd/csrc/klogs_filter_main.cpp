@@ -3,7 +3,7 @@
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
 //                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
-//                [--merge [--merge-timestamps]]
+//                [--merge [--merge-timestamps]] [--top K [--top-mask-digits] [--top-key-bytes N]]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
 //
 // -A / -B / -C N (lines of context after / before / around a matching line) and
@@ -23,6 +23,12 @@
 // --merge also writes <logpath>/merged.log: the emitted lines of all containers in one
 // chronological sequence (SPEC.md S4d, klf_result_timeline), each behind "<pod>/<container> ";
 // --merge-timestamps keeps each line's timestamp.  The per-container files stay as they are.
+//
+// --top K (1..65536) also writes <logpath>/top.tsv: the K most frequent messages of the selection
+// (after the pattern, the context flags and the window; before --since and --tail, SPEC.md S4e,
+// klf_result_groups) over all containers, with their line counts and their first and last line.
+// --top-mask-digits counts messages that differ only in their numbers as one (each run of
+// digits shows as '#'); --top-key-bytes N compares the first N bytes of a message only.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -83,6 +89,10 @@ void usage() {
                "                    [--merge [--merge-timestamps]]   (also writes <logpath>/merged.log: the emitted\n"
                "                    lines of all containers by time, each behind \"<pod>/<container> \"; with their\n"
                "                    timestamps)\n"
+               "                    [--top K [--top-mask-digits] [--top-key-bytes N]]   (also writes <logpath>/top.tsv:\n"
+               "                    the K most frequent messages of the selected lines, K in 1..65536, over all\n"
+               "                    containers; with each run of digits counted as '#'; comparing the first N\n"
+               "                    bytes of a message only; counted before --since / --tail apply)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -103,6 +113,14 @@ int main(int argc, char** argv) {
   std::string hist_arg;
   bool hist_set = false;  // --histogram
   bool merge = false, merge_ts = false;  // --merge, --merge-timestamps
+  klf_groups_opts top{0, 0, 0, 0};
+  bool top_set = false, top_mask = false, top_key_set = false;  // --top, --top-mask-digits, --top-key-bytes
+  auto number = [&](const std::string& v, unsigned long long max) -> uint32_t {
+    char* end = nullptr;
+    const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
+    if (v.empty() || v[0] < '0' || v[0] > '9' || *end || x > max) usage();
+    return (uint32_t)x;
+  };
   auto context = [&](const std::string& v) -> uint32_t {
     char* end = nullptr;
     const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
@@ -131,6 +149,9 @@ int main(int argc, char** argv) {
     else if (a == "--histogram") { hist_arg = val(); hist_set = true; }
     else if (a == "--merge") merge = true;
     else if (a == "--merge-timestamps") merge_ts = true;
+    else if (a == "--top") { top.top = number(val(), KLF_GROUPS_MAX_TOP); top_set = true; }
+    else if (a == "--top-mask-digits") top_mask = true;
+    else if (a == "--top-key-bytes") { top.max_key = number(val(), 0xFFFFFFFFull); top_key_set = true; }
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -148,6 +169,8 @@ int main(int argc, char** argv) {
   if (manifest.empty()) usage();
   if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
   if (merge_ts && !merge) usage();
+  if ((top_set && top.top == 0) || ((top_mask || top_key_set) && !top_set)) usage();
+  if (top_mask) top.flags |= KLF_GROUPS_MASK_DIGITS;
   // --from / --until: an instant, or a duration before `now` (--now may follow them)
   klf_window_opts window{{KLF_TIME_MIN_SEC, 0, 0}, {KLF_TIME_MAX_SEC, 0, 0},
                          regroup.before, regroup.after, regroup.flags, 0};
@@ -329,6 +352,36 @@ int main(int argc, char** argv) {
           std::fprintf(hf, "%s\t%s\tabove\t%llu\n", pod, cname[i].c_str(), (unsigned long long)ho[2 * (size_t)i + 1]);
       }
       if (std::fclose(hf) != 0) panic_exit("close " + hpath);
+    }
+    if (top_set) {  // the most frequent messages of the result that gets written, before it is
+      klf_groups* gr = nullptr;
+      rc = klf_result_groups(r, &top, &gr);
+      if (rc != KLF_OK) panic_exit(std::string("klf_result_groups: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      const klf_group_entry* ge = nullptr;
+      const uint8_t* keys = nullptr;
+      uint64_t ng = 0, nk = 0;
+      rc = klf_groups_entries(gr, &ge, &ng);
+      if (rc == KLF_OK) rc = klf_groups_keys(gr, &keys, &nk);
+      if (rc != KLF_OK) panic_exit(std::string("klf_groups_entries: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      const std::string tpath = logpath + "/top.tsv";
+      FILE* tf = std::fopen(tpath.c_str(), "w");
+      if (!tf) panic_exit("create " + tpath);
+      std::fprintf(tf, "Lines\tFirstPod\tFirstContainer\tFirstLine\tLastPod\tLastContainer\tLastLine\tKey\n");
+      for (uint64_t k = 0; k < ng; ++k) {
+        const klf_group_entry& x = ge[k];
+        std::fprintf(tf, "%llu\t%s\t%s\t%llu\t%s\t%s\t%llu\t", (unsigned long long)x.count,
+                     pods[table[x.first_stream].pod].name.c_str(), cname[x.first_stream].c_str(),
+                     (unsigned long long)x.first_line + 1, pods[table[x.last_stream].pod].name.c_str(),
+                     cname[x.last_stream].c_str(), (unsigned long long)x.last_line + 1);
+        for (uint32_t b = 0; b < x.key_len; ++b) {  // every byte outside printable ASCII, and '\\', as \xHH
+          const uint8_t c = keys[x.key_off + b];
+          if (c < 0x20 || c >= 0x7f || c == '\\') std::fprintf(tf, "\\x%02X", c);
+          else std::fputc(c, tf);
+        }
+        std::fputc('\n', tf);
+      }
+      if (std::fclose(tf) != 0) panic_exit("close " + tpath);
+      klf_groups_free(gr);
     }
     if (merge) {  // the timeline of the result that gets written, beside the per-container files
       std::string tags;

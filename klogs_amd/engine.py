@@ -33,6 +33,9 @@ TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, ope
 HIST_MAX_BUCKETS = 65536      # KLF_HIST_MAX_BUCKETS: klf_hist_opts.n_buckets at most
 TIMELINE_TIMESTAMPS = 1       # KLF_TIMELINE_TIMESTAMPS: render each line's prefix too
 TIMELINE_MAX_TAG = 1024       # KLF_TIMELINE_MAX_TAG: bytes of one stream's tag at most
+GROUPS_MASK_DIGITS = 1        # KLF_GROUPS_MASK_DIGITS: each run of ASCII digits in a key becomes one '#'
+GROUPS_MAX_TOP = 65536        # KLF_GROUPS_MAX_TOP: klf_groups_opts.top at most
+GROUPS_MAX_GROUPS = 1 << 26   # KLF_GROUPS_MAX_GROUPS: klf_groups_opts.max_groups at most
 
 MODE_NAMES = {0: "none", 1: "never", 2: "all", 3: "literal1", 4: "general"}
 
@@ -79,6 +82,20 @@ class _TimelineOpts(C.Structure):
 
 # klf_timeline_entry (32 bytes)
 TIMELINE_ENTRY = np.dtype([("sec", "<i8"), ("nsec", "<i4"), ("stream", "<u4"), ("line", "<u8"), ("off", "<u8")])
+
+
+class _GroupsOpts(C.Structure):
+    _fields_ = [("top", C.c_uint32), ("max_groups", C.c_uint32), ("max_key", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _GroupEntry(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("first_line", C.c_uint64), ("last_line", C.c_uint64), ("key_off", C.c_uint64),
+                ("first_stream", C.c_uint32), ("last_stream", C.c_uint32), ("key_len", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# klf_group_entry (48 bytes)
+GROUP_ENTRY = np.dtype([("count", "<u8"), ("first_line", "<u8"), ("last_line", "<u8"), ("key_off", "<u8"),
+                        ("first_stream", "<u4"), ("last_stream", "<u4"), ("key_len", "<u4"), ("_pad", "<u4")])
 
 
 class _Counts(C.Structure):
@@ -130,6 +147,14 @@ SIGNATURES = {
     "klf_timeline_write": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "klf_timeline_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "klf_timeline_free": (None, [C.c_void_p]),
+    "klf_result_groups": (C.c_int, [C.c_void_p, C.POINTER(_GroupsOpts), C.POINTER(C.c_void_p)]),
+    "klf_groups_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "klf_groups_keys": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "klf_groups_totals": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "klf_groups_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "klf_groups_free": (None, [C.c_void_p]),
+    "klf_group_key": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                C.POINTER(C.c_size_t)]),
     "klf_follow_open": (C.c_int, [C.c_void_p, C.POINTER(_Filter), C.POINTER(C.c_void_p)]),
     "klf_follow_feed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
     "klf_follow_flush": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -366,6 +391,81 @@ class Timeline:
             self._p = C.c_void_p()
 
 
+def group_key(content: bytes, max_key: int = 0, flags: int = 0) -> bytes:
+    """klf_group_key: the SPEC.md S4e key of one content (without its '\\n'), by the normaliser
+    the kernels run.  No GPU."""
+    content = bytes(content)
+    src = C.create_string_buffer(content, len(content) or 1)
+    n = C.c_size_t()
+    out = C.create_string_buffer(len(content) or 1)
+    _check(_lib.klf_group_key(C.addressof(src), len(content), int(max_key), int(flags), C.addressof(out),
+                              len(content), C.byref(n)))
+    return out.raw[: n.value]
+
+
+class Groups:
+    """Grouped counts (klf_groups): `entries` is a numpy structured array (GROUP_ENTRY: count,
+    first_line, last_line, key_off, first_stream, last_stream, key_len) in result order,
+    `keys()` the entries' key bytes."""
+
+    def __init__(self, ptr: int, eng):
+        self._p = C.c_void_p(ptr)
+        self._eng = eng
+
+    @property
+    def entries(self) -> np.ndarray:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.klf_groups_entries(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        if not n.value:
+            return np.zeros(0, dtype=GROUP_ENTRY)
+        return np.frombuffer(C.string_at(p.value, n.value * GROUP_ENTRY.itemsize), dtype=GROUP_ENTRY).copy()
+
+    def __len__(self) -> int:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.klf_groups_entries(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        return int(n.value)
+
+    @property
+    def key_bytes(self) -> bytes:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.klf_groups_keys(self._p, C.byref(p), C.byref(n)), self._eng._h)
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def keys(self) -> List[bytes]:
+        blob = self.key_bytes
+        return [blob[int(e["key_off"]): int(e["key_off"]) + int(e["key_len"])] for e in self.entries]
+
+    def _totals(self) -> Tuple[int, int]:
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(_lib.klf_groups_totals(self._p, C.byref(a), C.byref(b)), self._eng._h)
+        return int(a.value), int(b.value)
+
+    @property
+    def n_groups(self) -> int:
+        return self._totals()[0]
+
+    @property
+    def n_lines(self) -> int:
+        return self._totals()[1]
+
+    @property
+    def ms(self) -> float:
+        v = C.c_double()
+        _check(_lib.klf_groups_ms(self._p, C.byref(v)), self._eng._h)
+        return float(v.value)
+
+    def free(self):
+        if self._p:
+            _lib.klf_groups_free(self._p)
+            self._p = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 @dataclass
 class StreamOut:
     out: bytes
@@ -466,6 +566,18 @@ class Result:
         _check(_lib.klf_result_timeline(self._p, C.byref(o), C.byref(p)), self._eng._h)
         del keep
         return Timeline(p.value, self._eng)
+
+    def groups(self, top: int, mask_digits: bool = False, max_key: int = 0, max_groups: int = 0) -> "Groups":
+        """klf_result_groups (SPEC.md S4e): the lines of the set this result was selected from
+        (M, G' or G''; the parsed lines without patterns), before --since and --tail, grouped by
+        key: the content without its '\\n', cut to max_key bytes (0: all), with each run of digits
+        as one '#' when mask_digits.  The first `top` groups by (count descending, first line
+        ascending).  Read-only: this result stays the latest and valid.  The Groups object owns
+        its buffers: it outlives later runs and must be freed before the engine is closed."""
+        o = _GroupsOpts(int(top), int(max_groups), int(max_key), GROUPS_MASK_DIGITS if mask_digits else 0)
+        p = C.c_void_p()
+        _check(_lib.klf_result_groups(self._p, C.byref(o), C.byref(p)), self._eng._h)
+        return Groups(p.value, self._eng)
 
     def last_unparsed(self, i: int) -> int:
         """klf_result_last_unparsed: rank from the end (over newline-terminated lines) of the
