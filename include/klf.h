@@ -466,6 +466,83 @@ void klf_groups_free(klf_groups* g);
 int klf_group_key(const uint8_t* content, size_t len, uint32_t max_key, uint32_t flags,
                   uint8_t* out, size_t cap, size_t* n);
 
+/* ---- numeric field statistics (SPEC.md S4f; --stat KEY) ------------------------------ */
+/* How slow: the statistics of a numeric field such as latency_ms= or took= over the set r was
+ * selected from, without copying a line to the host.  For a result r that is the engine's latest,
+ * H is klf_result_histogram's and klf_result_groups' H: the parsed lines of M (a run's result or a
+ * klf_retail of one), G' (klf_regroup), G'' (klf_window), or every parsed line on a run's result
+ * of an engine without patterns; taken before --since and --tail, like klf_counts.matched.
+ * Each line of H is classified from its content C alone (its S1 content without the terminating
+ * '\n'; a '\r' stays; an unterminated fragment like a terminated line).  A line in which `key`
+ * (1..64 arbitrary bytes, compared bytewise) does not occur is a miss.  Otherwise only the key's
+ * first occurrence counts: behind it at most 4 bytes of { ' ', '\t', '=', ':', '"' } are skipped,
+ * then an optional single '-' or '+', then a run of ASCII digits of any length (at least one)
+ * and, if a '.' and a digit follow, a run of fraction digits.  Where a digit is missing, or C
+ * ends first, the line is bad: the key is there, a value is not.  Plain mode: the value is the
+ * number in units of 10^-decimals, cut toward zero ("12.3456" with decimals = 2 is 1234);
+ * whatever follows the number is ignored ("12ms" is 12, "1e5" is 1).  With KLF_FIELD_DURATION
+ * (decimals = 0) the value is nanoseconds by the prefix grammar of Go's time.ParseDuration: one or
+ * more components number-then-unit with nothing between them (ns, us, µs, μs, ms, s, m, h,
+ * longest match first; another component follows iff the next byte is a digit; the sign stands
+ * before the first only), each worth int * unit + floor(first 9 fraction digits * unit / 1e9);
+ * a component without a unit (a bare number too) makes the line bad.  A magnitude (a duration's
+ * total) of 2^62 or more makes the line bad.  Every other line is a hit with |value| < 2^62.
+ * rows[i] is stream i's row (a zero row for a stream without bytes), rows[n_streams] the row over
+ * all streams: lines = |H|, hits, bad (misses = lines - hits - bad), min / max over the hits,
+ * their exact sum as a 128-bit two's-complement pair, and the lowest (stream id, line number)
+ * whose value is min / max; lines are 0-based in their streams.  Without a hit min = max = sum =
+ * 0, the *_line fields are UINT64_MAX and the *_stream fields UINT32_MAX.  qvals[i * n_quantiles +
+ * k] is row i's quantile quantiles[k] (permyriad, any order, duplicates allowed) by nearest rank:
+ * of the row's n hits in ascending order the one at index max(1, ceil(q n / 10000)) - 1, so
+ * 0 is min and 10000 is max; 0 with n = 0.
+ * Read-only like klf_result_histogram: r stays the latest result and stays valid, nothing of it
+ * is written, and the call may be repeated with other options.  Read again: the selection
+ * bitmap (L/8 bytes; the line meta, 2 L, without patterns) and, per line of H, its line-index
+ * entry (built now if the run left it out), its meta and its content bytes in the batch, which
+ * must still be resident (klf_run_device: the caller's buffer).  On an engine without patterns
+ * that is a second full read of the batch.  The outputs are the caller's arrays; all device
+ * scratch (12 bytes per line of H, 32 per hit) is freed before the call returns, and two calls
+ * with the same options give the same bytes.  *ms (nullable): device time of the call, first
+ * launch to last.
+ * KLF_EINVAL (checked first, without touching the device): null r, o, rows or key; key_len
+ * outside 1..KLF_FIELD_MAX_KEY; decimals above 9, or non-zero with KLF_FIELD_DURATION; unknown
+ * flag bits; n_quantiles above KLF_FIELD_MAX_QUANTILES; a quantile above 10000; null qvals or
+ * quantiles with n_quantiles > 0.  KLF_ESTATE: r is not the engine's latest result.
+ * KLF_ETOOBIG: 2^32 or more lines in H.  KLF_ENOMEM: an allocation failed.  Not promised: follow
+ * sessions (a flush's statistics cover that flush) and shard.run_split.  Replaces nothing in the
+ * reference, whose per-container files (cmd/root.go:341-374) stay as they are. */
+#define KLF_FIELD_DURATION 1u
+#define KLF_FIELD_MAX_KEY 64u
+#define KLF_FIELD_MAX_QUANTILES 16u
+typedef struct klf_field_opts {      /* 32 bytes */
+  const uint8_t* key;
+  const uint16_t* quantiles;         /* n_quantiles permyriad values; may be NULL iff n_quantiles == 0 */
+  uint32_t key_len;                  /* 1 .. KLF_FIELD_MAX_KEY */
+  uint32_t decimals;                 /* 0 .. 9; 0 with KLF_FIELD_DURATION */
+  uint32_t n_quantiles;              /* 0 .. KLF_FIELD_MAX_QUANTILES */
+  uint32_t flags;                    /* KLF_FIELD_* */
+} klf_field_opts;
+typedef struct klf_field_row {       /* 80 bytes */
+  uint64_t lines, hits, bad;
+  int64_t min, max;
+  uint64_t sum_lo; int64_t sum_hi;
+  uint64_t min_line, max_line;
+  uint32_t min_stream, max_stream;
+} klf_field_row;
+int klf_result_field_stats(klf_result* r, const klf_field_opts* o, klf_field_row* rows /* n_streams + 1 */,
+                           int64_t* qvals /* (n_streams + 1) * n_quantiles; NULL iff n_quantiles == 0 */,
+                           double* ms /* nullable: device time, first launch to last */);
+/* Host helper, no GPU: the S4f class and value of one content (without its '\n'), by the extractor
+ * the kernels run (klf_fieldval.hpp).  Returns KLF_FIELD_HIT with *value set, KLF_FIELD_MISS or
+ * KLF_FIELD_BAD (*value = 0), or KLF_EINVAL: a null content with len > 0, a null key or value,
+ * key_len outside 1..KLF_FIELD_MAX_KEY, decimals above 9 or non-zero with KLF_FIELD_DURATION,
+ * unknown flag bits. */
+#define KLF_FIELD_HIT 0
+#define KLF_FIELD_MISS 1
+#define KLF_FIELD_BAD 2
+int klf_field_value(const uint8_t* content, size_t len, const uint8_t* key, uint32_t key_len,
+                    uint32_t decimals, uint32_t flags, int64_t* value);
+
 /* ---- follow mode (-f) -------------------------------------------- */
 /* The reference streams each container until EOF with Follow set (cmd/root.go:217-218,
  * streamLog :312-339, the "ended prematurely" warning :314-318) while the main goroutine

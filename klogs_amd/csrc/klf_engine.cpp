@@ -23,6 +23,7 @@
 #include "../../include/klf.h"
 #include "../../include/klf_debug.h"
 #include "klf_copypool.hpp"
+#include "klf_fieldval.hpp"
 #include "klf_groupkey.hpp"
 #include "klf_kernels.hpp"
 #include "klf_patterns.hpp"
@@ -2831,6 +2832,206 @@ extern "C" int klf_group_key(const uint8_t* content, size_t len, uint32_t max_ke
     if (nm.step(content[i], c)) out[k++] = c;
   }
   return KLF_OK;
+}
+
+// ------------------------------------------------------- numeric field statistics ---
+
+static_assert(sizeof(klf_field_opts) == 32 && sizeof(klf_field_row) == 80, "klf_field_opts / klf_field_row layout");
+static_assert(KLF_FIELD_DURATION == klf::kFieldDuration && KLF_FIELD_MAX_KEY == klf::kFieldMaxKey &&
+                  KLF_FIELD_MAX_KEY == klf::kFsMaxKey && KLF_FIELD_MAX_QUANTILES == klf::kFsMaxQuantiles &&
+                  KLF_FIELD_HIT == klf::kFieldHit && KLF_FIELD_MISS == klf::kFieldMiss && KLF_FIELD_BAD == klf::kFieldBad,
+              "one set of values for the host helper and the kernels");
+
+namespace {
+// The call's scratch: the chunk bases of the lines and of the hits, the per-line values and
+// classes, both item buffers, the histograms, the block counts, and the result block (the
+// per-segment table, the segments' hit prefix, the rows, the quantile values); freed when
+// klf_result_field_stats returns.
+struct FsScratch {
+  DevBuf cbase, hbase, val, cs, items[2], dhist, bcnt, res;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~FsScratch() {
+    for (DevBuf* b : {&cbase, &hbase, &val, &cs, &items[0], &items[1], &dhist, &bcnt, &res}) b->release();
+    for (auto& x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+}  // namespace
+
+static int fs_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
+  const hipError_t h = b.ensure(bytes);
+  if (h == hipSuccess) return KLF_OK;
+  (void)hipGetLastError();
+  if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string("klf_result_field_stats: alloc ") + what);
+  return hip_err(e, h, what);
+}
+
+static bool field_opts_ok(const uint8_t* key, uint32_t key_len, uint32_t decimals, uint32_t flags) {
+  return key && key_len >= 1 && key_len <= KLF_FIELD_MAX_KEY && !(flags & ~KLF_FIELD_DURATION) && decimals <= 9 &&
+         !((flags & KLF_FIELD_DURATION) && decimals);
+}
+
+extern "C" int klf_result_field_stats(klf_result* r, const klf_field_opts* o, klf_field_row* rows, int64_t* qvals,
+                                      double* ms) {
+  if (!r || !o || !rows) return KLF_EINVAL;
+  klf_engine* e = r->e;
+  if (!field_opts_ok(o->key, o->key_len, o->decimals, o->flags))
+    return set_err(e, KLF_EINVAL, "klf_result_field_stats: key of 1 .. 64 bytes, decimals 0 .. 9 (0 with "
+                                  "KLF_FIELD_DURATION), no unknown flag bits");
+  if (o->n_quantiles > KLF_FIELD_MAX_QUANTILES || (o->n_quantiles && (!o->quantiles || !qvals)))
+    return set_err(e, KLF_EINVAL, "klf_result_field_stats: at most 16 quantiles, with their arrays");
+  for (uint32_t k = 0; k < o->n_quantiles; ++k)
+    if (o->quantiles[k] > 10000) return set_err(e, KLF_EINVAL, "klf_result_field_stats: a quantile above 10000");
+  if (int rc = check_latest(e, r, "klf_result_field_stats")) return rc;
+  const uint32_t nsegs = (uint32_t)r->so.size(), nq = o->n_quantiles, nrows = r->n_streams + 1;
+  if (ms) *ms = 0.0;
+  for (uint32_t i = 0; i < nrows; ++i) {
+    rows[i] = klf_field_row{};
+    rows[i].min_line = rows[i].max_line = UINT64_MAX;
+    rows[i].min_stream = rows[i].max_stream = UINT32_MAX;
+  }
+  if (nq) memset(qvals, 0, (size_t)nrows * nq * 8);
+  if (!nsegs) return KLF_OK;  // no stream has bytes
+  if (nsegs >> 30) return set_err(e, KLF_ETOOBIG, "klf_result_field_stats: 2^30 or more streams with bytes");
+  if (int rc = ensure_index(e)) return rc;
+  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+  hipStream_t st = e->stream;
+  FsScratch sc;
+  klf::FieldArgs g{};
+  g.v = sel_view(r);
+  memcpy(g.key, o->key, o->key_len);
+  g.key_len = o->key_len;
+  g.decimals = o->decimals;
+  g.flags = o->flags;
+  g.n_q = nq;
+  for (uint32_t k = 0; k < nq; ++k) g.q[k] = o->quantiles[k];
+  if (int rc = fs_alloc(e, sc.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
+  if (int rc = fs_alloc(e, sc.hbase, (g.v.nchunks + 1) * 8, "chunk hit bases")) return rc;
+  g.cbase = sc.cbase.as<uint64_t>();
+  g.hbase = sc.hbase.as<uint64_t>();
+  // the result block: the table, the segments' hit prefix, the rows, the quantile values
+  const size_t tab_w = (size_t)klf::kFsTabRows * nsegs, hpre_w = (size_t)nsegs + 1,
+               rows_w = ((size_t)nsegs + 1) * (sizeof(klf::FsRow) / 8), qv_w = ((size_t)nsegs + 1) * nq;
+  const size_t res_w = tab_w + hpre_w + rows_w + qv_w;
+  if (int rc = fs_alloc(e, sc.res, res_w * 8, "result block")) return rc;
+  g.tab = sc.res.as<uint64_t>();
+  g.hpre = g.tab + tab_w;
+  g.rows = reinterpret_cast<klf::FsRow*>(g.hpre + hpre_w);
+  g.qv = reinterpret_cast<int64_t*>(g.hpre + hpre_w + rows_w);
+  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "field statistics events");
+  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record field statistics start");
+  // 1. H lines per chunk -> n
+  HIPCHK(e, klf::launch_fs_count(g, st, e->num_cus), "launch k_fs_count");
+  uint64_t n = 0;
+  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics size");
+  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics size");
+  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_field_stats: 2^32 or more lines in the selection");
+  g.n = n;
+  // 2. every line's class and value; per segment the counts and the sum; the hits per chunk -> n_hits
+  if (int rc = fs_alloc(e, sc.val, (size_t)n * 8, "values")) return rc;
+  if (int rc = fs_alloc(e, sc.cs, (size_t)n * 4, "classes")) return rc;
+  g.val = sc.val.as<int64_t>();
+  g.cs = sc.cs.as<uint32_t>();
+  HIPCHK(e, klf::launch_fs_extract(g, st, e->num_cus), "launch k_fs_extract");
+  uint64_t n_hits = 0;
+  HIPCHK(e, hipMemcpyAsync(&n_hits, g.hbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics hits");
+  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics hits");
+  g.n_hits = n_hits;
+  // 3. the hits as sort items; value order -> the all-streams row; (segment, value) order -> the rest
+  klf::TlArgs tg{};
+  tg.n = n_hits;
+  uint32_t cur = 0;
+  if (n_hits) {
+    for (int k = 0; k < 2; ++k) {
+      if (int rc = fs_alloc(e, sc.items[k], (size_t)n_hits * sizeof(klf::TlItem), "sort items")) return rc;
+      tg.items[k] = sc.items[k].as<klf::TlItem>();
+    }
+    if (int rc = fs_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
+    g.items = tg.items[0];
+    g.dhist = tg.dhist = sc.dhist.as<uint64_t>();
+    HIPCHK(e, klf::launch_fs_compact(g, st, e->num_cus), "launch k_fs_compact");
+  }
+  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
+  if (n_hits) {
+    HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
+    HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
+  }
+  const size_t nblocks = (size_t)((n_hits + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
+  auto passes = [&](uint32_t p0, uint32_t p1) -> int {  // the passes whose digit differs somewhere
+    for (uint32_t p = p0; p < p1 && n_hits; ++p) {
+      bool one_bin = false;
+      for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n_hits;
+      if (one_bin) continue;
+      if (!tg.bcnt) {
+        if (int rc = fs_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
+        tg.bcnt = sc.bcnt.as<uint32_t>();
+      }
+      HIPCHK(e, klf::launch_tl_pass(tg, p, cur, st), "launch radix pass");
+      cur ^= 1u;
+    }
+    return KLF_OK;
+  };
+  if (int rc = passes(0, 8)) return rc;
+  HIPCHK(e, klf::launch_fs_rows(g, tg.items[cur], 1u, st), "launch k_fs_rows");
+  if (int rc = passes(8, klf::kTlDigits)) return rc;
+  HIPCHK(e, klf::launch_fs_rows(g, tg.items[cur], 0u, st), "launch k_fs_rows");
+  // 4. one copy of the result block; segments -> stream ids; the all-streams counts and sum
+  std::vector<uint64_t> res(res_w);
+  HIPCHK(e, hipEventRecord(sc.ev[1], st), "record field statistics end");
+  HIPCHK(e, hipMemcpyAsync(res.data(), g.tab, res_w * 8, hipMemcpyDeviceToHost, st), "D2H field statistics");
+  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics");
+  if (ms) {
+    float f = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "field statistics timing");
+    *ms = f;
+  }
+  std::vector<uint32_t> segstream(nsegs, 0u);
+  for (uint32_t id = 0; id < r->n_streams; ++id)
+    if (r->seg_of[id] >= 0) segstream[(size_t)r->seg_of[id]] = id;
+  const uint64_t* tab = res.data();
+  const klf::FsRow* drows = reinterpret_cast<const klf::FsRow*>(res.data() + tab_w + hpre_w);
+  const int64_t* dqv = reinterpret_cast<const int64_t*>(res.data() + tab_w + hpre_w + rows_w);
+  auto place = [&](klf_field_row& out, const klf::FsRow& d, __int128 sum) {
+    out.sum_lo = (uint64_t)(unsigned __int128)sum;
+    out.sum_hi = (int64_t)(sum >> 64);
+    if (!out.hits) return;
+    out.min = d.min;
+    out.max = d.max;
+    out.min_line = d.min_line;
+    out.max_line = d.max_line;
+    out.min_stream = d.min_seg < nsegs ? segstream[d.min_seg] : UINT32_MAX;
+    out.max_stream = d.max_seg < nsegs ? segstream[d.max_seg] : UINT32_MAX;
+  };
+  klf_field_row& all = rows[r->n_streams];
+  __int128 all_sum = 0;
+  for (uint32_t s = 0; s < nsegs; ++s) {
+    klf_field_row& out = rows[segstream[s]];
+    out.lines = tab[s];
+    out.hits = tab[(size_t)nsegs + s];
+    out.bad = tab[2 * (size_t)nsegs + s];
+    // the sum of v = (v >> 32) * 2^32 + (v & 0xFFFFFFFF) over the hits, from its two halves
+    const __int128 sum = (__int128)(int64_t)tab[3 * (size_t)nsegs + s] * ((__int128)1 << 32) + (__int128)tab[4 * (size_t)nsegs + s];
+    place(out, drows[s], sum);
+    if (nq) memcpy(qvals + (size_t)segstream[s] * nq, dqv + (size_t)s * nq, (size_t)nq * 8);
+    all.lines += out.lines;
+    all.hits += out.hits;
+    all.bad += out.bad;
+    all_sum += sum;
+  }
+  place(all, drows[nsegs], all_sum);
+  if (nq) memcpy(qvals + (size_t)r->n_streams * nq, dqv + (size_t)nsegs * nq, (size_t)nq * 8);
+  return KLF_OK;
+}
+
+extern "C" int klf_field_value(const uint8_t* content, size_t len, const uint8_t* key, uint32_t key_len,
+                               uint32_t decimals, uint32_t flags, int64_t* value) {
+  if ((!content && len) || !value || !field_opts_ok(key, key_len, decimals, flags)) return KLF_EINVAL;
+  *value = 0;
+  klf::FieldHostBytes src{content};
+  int64_t v = 0;
+  const int cls = klf::field_classify(src, (uint64_t)len, key, key_len, decimals, flags, &v);
+  if (cls == klf::kFieldHit) *value = v;
+  return cls;
 }
 
 extern "C" int klf_result_last_unparsed(klf_result* r, uint32_t id, uint64_t* rank) {

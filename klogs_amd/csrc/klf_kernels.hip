@@ -21,6 +21,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "klf_fieldval.hpp"
 #include "klf_groupkey.hpp"
 #include "klf_kernels.hpp"
 #include "klf_ts.hpp"
@@ -3635,14 +3636,19 @@ struct GrLine {
   const uint8_t* p;
   uint64_t n;
 };
-__device__ __forceinline__ GrLine gr_line(const GroupArgs& g, uint64_t l, uint32_t s) {
-  const SegDesc sd = g.v.segs[s];
-  const uint64_t ls = g.v.line_off[l + s], le = g.v.line_off[l + s + 1];
-  const uint8_t* segp = g.v.bytes + sd.base;
-  const uint32_t plen = line_plen(g, g.v.meta[l], segp, ls, le);
+// S1's content of line l (of segment s) without its terminating '\n'.
+__device__ __forceinline__ GrLine sel_content(const SelView& v, uint64_t l, uint32_t s) {
+  const SegDesc sd = v.segs[s];
+  const uint64_t ls = v.line_off[l + s], le = v.line_off[l + s + 1];
+  const uint8_t* segp = v.bytes + sd.base;
+  const uint32_t plen = line_plen(v, v.meta[l], segp, ls, le);
   uint64_t n = le - ls - plen;
-  if (n && !(le == sd.len && g.v.segout[s].frag)) --n;  // the terminating '\n'
-  return {segp + ls + plen, group_key_span(n, g.max_key)};
+  if (n && !(le == sd.len && v.segout[s].frag)) --n;  // the terminating '\n'
+  return {segp + ls + plen, n};
+}
+__device__ __forceinline__ GrLine gr_line(const GroupArgs& g, uint64_t l, uint32_t s) {
+  const GrLine q = sel_content(g.v, l, s);
+  return {q.p, group_key_span(q.n, g.max_key)};
 }
 // The key bytes of a line, one after the other.  A 16-B load may reach 15 bytes past the span:
 // into the next line, the next stream or the allocation's slack (kAllocSlack), never used.
@@ -3866,6 +3872,254 @@ __global__ __launch_bounds__(256) void k_gr_render(GroupArgs g, const TlItem* __
     });
   }
   if (lane == 0) g.entries[i] = e;
+}
+
+// ================================ numeric field statistics (klf_result_field_stats, SPEC.md S4f) ==
+// k_fs_extract is the selected-line walk over H, one lane per line: the lane runs the extractor of
+// klf_fieldval.hpp over its content and leaves the line's value and class at the line's rank in H.
+// The hits then become sort items keyed by (segment, value); after the value digits of the
+// timeline's radix passes the items are in value order (the all-streams row), after the segment
+// digits in (segment, value) order (the segments' rows): k_fs_rows reads minimum, maximum and the
+// quantile ranks straight out of the sorted items.
+
+// The content's bytes through 16-B loads at multiples of 16 from its start.  A load may reach 15
+// bytes past the content: into the next line, the next stream or the allocation's slack
+// (kAllocSlack); at(i) is only asked for i inside the content, so none of them is ever looked at.
+struct FsBytes {
+  const uint8_t* p;
+  uint64_t blk, lo, hi;
+  __device__ __forceinline__ explicit FsBytes(const uint8_t* q) : p(q), blk(~0ull), lo(0), hi(0) {}
+  __device__ __forceinline__ uint8_t at(uint64_t i) {
+    const uint64_t b = i >> 4;
+    if (b != blk) {
+      typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+      u64x2 x;
+      __builtin_memcpy(&x, p + (b << 4), 16);
+      lo = x.x;
+      hi = x.y;
+      blk = b;
+    }
+    const uint32_t k = (uint32_t)i & 15u;
+    return (uint8_t)(k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8)));
+  }
+};
+
+__global__ __launch_bounds__(256) void k_fs_count(FieldArgs g) {
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t;
+    const uint32_t cnt = wave_sum((uint32_t)__popc(view_word(g.v, w, L)));
+    __syncthreads();  // (the previous chunk's sums are read)
+    if (lane == 0) s_w[wv] = cnt;
+    __syncthreads();
+    if (t == 0) g.cbase[c] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  }
+}
+
+__device__ __forceinline__ void fs_add(uint64_t* p, uint64_t x) {
+  if (x) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)x);
+}
+
+// A wave's counts and sums over a run of lines of one segment: lines / hits / bad are wave-uniform
+// (ballot popcounts), the two halves of the sum are per lane until flush() adds them all, once.
+struct FsAcc {
+  uint32_t seg;  // ~0: none
+  uint32_t lines, hits, bad;
+  uint64_t hi, lo;
+  __device__ __forceinline__ void flush(const FieldArgs& g, int lane) {  // (every lane of the wave calls it)
+    if (seg != ~0u) {
+      const uint64_t h = wave_sum(hi), l = wave_sum(lo);
+      if (lane == 0) {
+        const uint64_t ns = g.v.nsegs;
+        fs_add(g.tab + seg, lines);
+        fs_add(g.tab + ns + seg, hits);
+        fs_add(g.tab + 2 * ns + seg, bad);
+        fs_add(g.tab + 3 * ns + seg, h);
+        fs_add(g.tab + 4 * ns + seg, l);
+      }
+    }
+    seg = ~0u;
+    lines = hits = bad = 0;
+    hi = lo = 0;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_fs_extract(FieldArgs g) {
+  __shared__ WalkLds ws;
+  __shared__ uint32_t s_tot[4], s_hits[4];
+  __shared__ uint8_t s_key[kFsMaxKey];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (t < (int)kFsMaxKey) s_key[t] = g.key[t];
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  const uint64_t ns = g.v.nsegs;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t total = walk_publish(ws, g.v, view_word(g.v, w, L), l0);  // (its barrier: the last chunk's s_hits is read)
+    if (lane == 0) s_tot[wv] = total;
+    __syncthreads();  // (s_key too)
+    uint64_t base = g.cbase[c];
+    for (int k = 0; k < wv; ++k) base += s_tot[k];
+    FsAcc acc;
+    acc.seg = ~0u;
+    acc.flush(g, lane);
+    uint32_t chunk_hits = 0;
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
+      int cls = kFieldMiss;
+      int64_t v = 0;
+      if (q.live) {
+        const GrLine ln = sel_content(g.v, q.l, q.s);
+        FsBytes src(ln.p);
+        cls = field_classify(src, ln.n, s_key, g.key_len, g.decimals, g.flags, &v);
+        if (cls != kFieldHit) v = 0;
+        const uint64_t rank = base + q.k;
+        if (rank < g.n) {  // (always: n is the scan's total of the same words)
+          g.val[rank] = v;
+          g.cs[rank] = q.s << 2 | (uint32_t)cls;
+        }
+      }
+      const bool is_hit = q.live && cls == kFieldHit, is_bad = q.live && cls == kFieldBad;
+      const uint64_t live = __ballot(q.live), hit = __ballot(is_hit), bad = __ballot(is_bad);
+      chunk_hits += (uint32_t)__popcll(hit);
+      // (lane 0 has a line in every round)
+      const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q.live ? q.s : 0u));
+      const uint32_t s = q.live ? q.s : s0;
+      if (__all(s == s0)) {  // one segment: into the wave's run
+        if (acc.seg != s0) {
+          acc.flush(g, lane);
+          acc.seg = s0;
+        }
+        acc.lines += (uint32_t)__popcll(live);
+        acc.hits += (uint32_t)__popcll(hit);
+        acc.bad += (uint32_t)__popcll(bad);
+        if (is_hit) {
+          acc.hi += (uint64_t)(v >> 32);
+          acc.lo += (uint64_t)v & 0xFFFFFFFFull;
+        }
+      } else {  // a round over several (small) streams: a line at a time
+        acc.flush(g, lane);
+        if (q.live) {
+          fs_add(g.tab + s, 1);
+          fs_add(g.tab + ns + s, is_hit ? 1 : 0);
+          fs_add(g.tab + 2 * ns + s, is_bad ? 1 : 0);
+          if (is_hit) {
+            fs_add(g.tab + 3 * ns + s, (uint64_t)(v >> 32));
+            fs_add(g.tab + 4 * ns + s, (uint64_t)v & 0xFFFFFFFFull);
+          }
+        }
+      }
+    });
+    acc.flush(g, lane);
+    if (lane == 0) s_hits[wv] = chunk_hits;
+    __syncthreads();
+    if (t == 0) g.hbase[c] = (uint64_t)s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3];
+  }
+}
+
+// The segments' hits beside the table, for their prefix.
+__global__ __launch_bounds__(256) void k_fs_hcopy(FieldArgs g) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s < g.v.nsegs) g.hpre[s] = g.tab[(uint64_t)g.v.nsegs + s];
+}
+
+// One item per hit, at the chunk's hit base + its place among the chunk's hits: the ranks of
+// chunk c are [cbase[c], cbase[c + 1]).  Key: nsec = the low half of v ^ 2^63, sec_key = its high
+// half under the segment, so the digits 0..7 order by value and 8..11 by segment.
+__global__ __launch_bounds__(256) void k_fs_compact(FieldArgs g) {
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t r0 = g.cbase[c], r1 = g.cbase[c + 1];
+    uint64_t out = g.hbase[c];
+    for (uint64_t rb = r0; rb < r1; rb += 256) {  // (block-uniform)
+      const uint64_t rank = rb + t;
+      const bool valid = rank < r1 && rank < g.n;
+      const uint32_t x = valid ? g.cs[rank] : (uint32_t)kFieldMiss;
+      const uint32_t hit = (x & 3u) == (uint32_t)kFieldHit ? 1u : 0u;
+      uint32_t tot;
+      const uint32_t incl = block_incl_scan_u32(hit, s_w, &tot);
+      const uint64_t pos = out + incl - 1;
+      if (hit && pos < g.n_hits) {  // (always: n_hits is the scan's total of the same hits)
+        const uint64_t u = (uint64_t)g.val[rank] ^ (1ull << 63);
+        g.items[pos] = TlItem{(uint64_t)(x >> 2) << 32 | u >> 32, (uint32_t)u, (uint32_t)rank};
+      }
+      out += tot;
+    }
+  }
+}
+
+__device__ __forceinline__ int64_t fs_item_value(const TlItem& it) {
+  return (int64_t)(((it.sec_key & 0xFFFFFFFFull) << 32 | it.nsec) ^ (1ull << 63));
+}
+// The global line of rank `rank` of H: its chunk by the chunk bases, then the chunk's words.
+__device__ uint64_t fs_rank_line(const FieldArgs& g, uint64_t rank, uint64_t L) {
+  uint64_t lo = 0, hi = g.v.nchunks;  // the last chunk whose base is <= rank (a chunk without lines shares the next one's)
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (g.cbase[mid] <= rank) lo = mid; else hi = mid;
+  }
+  uint64_t r = rank - g.cbase[lo];
+  for (uint32_t k = 0; k < kMatchChunk / 32; ++k) {
+    const uint64_t w = lo * (kMatchChunk / 32) + k;
+    const uint32_t x = view_word(g.v, w, L), cnt = (uint32_t)__popc(x);
+    if (r < cnt) return w * 32 + nth_set_bit(x, (uint32_t)r);
+    r -= cnt;
+  }
+  return ~0ull;  // (never: rank < n)
+}
+
+// One block per row; its hits are sorted[a .. b) in value order.  Thread j < n_q: quantile j by
+// nearest rank; thread n_q: the minimum and its line (the range's first item: equal values keep
+// their rank order); thread n_q + 1: the maximum and the first item of its run of equal values.
+__global__ __launch_bounds__(64) void k_fs_rows(FieldArgs g, const TlItem* __restrict__ sorted, uint32_t all) {
+  const uint32_t row = all ? g.v.nsegs : blockIdx.x, j = threadIdx.x;
+  const uint64_t a = all ? 0ull : g.hpre[row], b = all ? g.n_hits : g.hpre[row + 1];
+  const uint64_t n = b > a && b <= g.n_hits ? b - a : 0ull;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  if (j < g.n_q) {
+    int64_t x = 0;
+    if (n) {
+      const uint64_t k = ((uint64_t)g.q[j] * n + 9999ull) / 10000ull;  // ceil(q n / 10000) <= n
+      x = fs_item_value(sorted[a + (k ? k - 1 : 0)]);
+    }
+    g.qv[(uint64_t)row * g.n_q + j] = x;
+  } else if (j == g.n_q || j == g.n_q + 1) {
+    const bool is_max = j != g.n_q;
+    int64_t x = 0;
+    uint64_t line = ~0ull;
+    uint32_t seg = ~0u;
+    if (n) {
+      uint64_t i = a;
+      if (is_max) {
+        x = fs_item_value(sorted[b - 1]);
+        uint64_t lo = a, hi = b - 1;  // the lowest i with value(i) >= x
+        while (lo < hi) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (fs_item_value(sorted[mid]) >= x) hi = mid; else lo = mid + 1;
+        }
+        i = lo;
+      } else {
+        x = fs_item_value(sorted[a]);
+      }
+      const uint64_t rank = sorted[i].ord;
+      const uint64_t l = rank < g.n ? fs_rank_line(g, rank, L) : ~0ull;
+      if (l < L) {
+        seg = find_seg_by_line(g.v.segout, g.v.nsegs, l);
+        line = l - g.v.segout[seg].line_lo;
+      }
+    }
+    FsRow* r = g.rows + row;
+    if (is_max) {
+      r->max = x;
+      r->max_line = line;
+      r->max_seg = seg;
+    } else {
+      r->min = x;
+      r->min_line = line;
+      r->min_seg = seg;
+    }
+  }
 }
 
 // Zeroes the run's counters and per-stream records (one launch instead of memsets).
@@ -5824,6 +6078,47 @@ hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t 
 hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_t st) {
   if (!g.top) return hipSuccess;
   hipLaunchKernelGGL(k_gr_render, dim3((g.top + 3) / 4), dim3(256), 0, st, g, sorted);
+  return hipGetLastError();
+}
+
+hipError_t launch_fs_count(const FieldArgs& g, hipStream_t st, int num_cus) {
+  if (g.v.nchunks) {
+    hipLaunchKernelGGL(k_fs_count, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.v.nchunks);
+  return hipGetLastError();
+}
+
+hipError_t launch_fs_extract(const FieldArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.tab, 0, (size_t)kFsTabRows * g.v.nsegs * 8, st);
+  if (e != hipSuccess) return e;
+  if (g.n && g.v.nchunks) {
+    hipLaunchKernelGGL(k_fs_extract, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else if ((e = hipMemsetAsync(g.hbase, 0, (size_t)g.v.nchunks * 8, st)) != hipSuccess) {
+    return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.hbase, g.v.nchunks);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_fs_hcopy, dim3((g.v.nsegs + 255) / 256), dim3(256), 0, st, g);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.hpre, (uint64_t)g.v.nsegs);
+  return hipGetLastError();
+}
+
+hipError_t launch_fs_compact(const FieldArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
+  if (e != hipSuccess || !g.n_hits || !g.v.nchunks) return e;
+  hipLaunchKernelGGL(k_fs_compact, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const uint64_t nb = (g.n_hits + 255) / 256, dmax = (uint64_t)num_cus * 8;
+  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items, g.n_hits, g.dhist);
+  return hipGetLastError();
+}
+
+hipError_t launch_fs_rows(const FieldArgs& g, const TlItem* sorted, uint32_t all, hipStream_t st) {
+  hipLaunchKernelGGL(k_fs_rows, dim3(all ? 1u : g.v.nsegs), dim3(64), 0, st, g, sorted, all);
   return hipGetLastError();
 }
 

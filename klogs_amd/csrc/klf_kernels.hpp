@@ -519,6 +519,63 @@ hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t 
 // k_gr_render: g.entries and g.keys from `sorted` and the scanned g.klen.
 hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_t stream);
 
+// Numeric field statistics of a finished run (klf_result_field_stats, SPEC.md S4f): per stream and
+// over all streams, how many lines of H carry `key` with a value behind it, and the minimum,
+// maximum, sum and nearest-rank quantiles of those values.
+//   k_fs_count / k_tl_scan    H lines per kMatchChunk chunk, their exclusive prefix -> n = |H|
+//   k_fs_extract              the selected-line walk over H, one lane per line: the extractor of
+//                             klf_fieldval.hpp over the content, 16 bytes a load; val[rank] /
+//                             cs[rank] = the line's value / segment and class, rank = its place in
+//                             H in (stream, line) order; per segment lines / hits / bad and the two
+//                             halves of the 128-bit sum (a wave adds once per run of lines of one
+//                             segment); hits per chunk
+//   k_tl_scan (twice)         the prefix of the chunks' hits -> n_hits; of the segments' hits
+//   k_fs_compact / k_tl_digits   one TlItem per hit, in rank order: key = (segment, value ^ 2^63),
+//                             ord = rank
+//   launch_tl_pass            the timeline's stable LSD passes: digits 0..7 order by value (then
+//                             k_fs_rows takes the all-streams row), digits 8..11 by segment (then
+//                             k_fs_rows takes the segments' rows)
+// Equal values keep their rank order, so the first item of a run of equal values is its lowest
+// (stream, line).  No kernel waits on another block: kernel boundaries are the only ordering.
+struct FsRow {        // what k_fs_rows leaves per row (the counts and sums are in FieldArgs::tab)
+  int64_t min, max;
+  uint64_t min_line, max_line;  // 0-based in their streams; ~0 without a hit
+  uint32_t min_seg, max_seg;    // ~0 without a hit
+};
+static_assert(sizeof(FsRow) == 40, "field rows");
+constexpr uint32_t kFsMaxQuantiles = 16;  // = KLF_FIELD_MAX_QUANTILES
+constexpr uint32_t kFsMaxKey = 64;        // = KLF_FIELD_MAX_KEY
+constexpr uint32_t kFsTabRows = 5;        // FieldArgs::tab: lines, hits, bad, sum_hi, sum_lo
+struct FieldArgs {
+  SelView v;                // bits_in null: the parsed lines (no patterns)
+  uint8_t key[kFsMaxKey];
+  uint32_t key_len, decimals, flags;  // klf_field_opts
+  uint32_t n_q;
+  uint16_t q[kFsMaxQuantiles];        // permyriad
+  uint64_t* cbase;          // [nchunks + 1] H lines per chunk, then their exclusive prefix and n
+  uint64_t n;               // |H| (known after launch_fs_count)
+  uint64_t* hbase;          // [nchunks + 1] hits per chunk, then their exclusive prefix and n_hits
+  uint64_t n_hits;          // (known after launch_fs_extract)
+  int64_t* val;             // [n] a hit's value (0 otherwise)
+  uint32_t* cs;             // [n] segment << 2 | class (klf_fieldval.hpp kField*)
+  uint64_t* tab;            // [kFsTabRows * nsegs] per segment (zeroed by launch_fs_extract): lines, hits, bad,
+                            // sum of v >> 32 (two's complement), sum of v & 0xFFFFFFFF
+  uint64_t* hpre;           // [nsegs + 1] the segments' hits, then their exclusive prefix and n_hits
+  TlItem* items;            // [n_hits] the sort's input
+  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_fs_compact)
+  FsRow* rows;              // [nsegs + 1]: the segments, then all streams
+  int64_t* qv;              // [(nsegs + 1) * n_q]
+};
+// k_fs_count + k_tl_scan: g.cbase[g.v.nchunks] = |H| afterwards.
+hipError_t launch_fs_count(const FieldArgs& g, hipStream_t stream, int num_cus);
+// Zeroes g.tab, then k_fs_extract and the two scans: g.hbase[g.v.nchunks] = n_hits afterwards.
+hipError_t launch_fs_extract(const FieldArgs& g, hipStream_t stream, int num_cus);
+// k_fs_compact into g.items, then g.dhist (k_tl_digits).
+hipError_t launch_fs_compact(const FieldArgs& g, hipStream_t stream, int num_cus);
+// k_fs_rows over `sorted` (null with n_hits = 0): all != 0 the all-streams row (items in value
+// order), else the segments' rows (items in (segment, value) order).
+hipError_t launch_fs_rows(const FieldArgs& g, const TlItem* sorted, uint32_t all, hipStream_t stream);
+
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the
 // scan, ev[3] after the general matcher, ev[4] after counts+tail+window prefix, ev[5]

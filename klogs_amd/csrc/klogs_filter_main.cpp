@@ -4,6 +4,7 @@
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
 //                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
 //                [--merge [--merge-timestamps]] [--top K [--top-mask-digits] [--top-key-bytes N]]
+//                [--stat KEY [--stat-decimals D | --stat-duration]]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
 //
 // -A / -B / -C N (lines of context after / before / around a matching line) and
@@ -29,6 +30,14 @@
 // klf_result_groups) over all containers, with their line counts and their first and last line.
 // --top-mask-digits counts messages that differ only in their numbers as one (each run of
 // digits shows as '#'); --top-key-bytes N compares the first N bytes of a message only.
+//
+// --stat KEY (1..64 bytes) also writes <logpath>/stats.tsv: the statistics of the number behind
+// the first KEY of each line of the selection (after the pattern, the context flags and the
+// window; before --since and --tail, SPEC.md S4f, klf_result_field_stats), one row per container
+// and one over all of them ("*"): pod, container, lines, hits, bad, min, max, sum, p50, p90, p99
+// and max_at = <pod>/<container>:<line, counted from 1> of the first line with the maximum; no
+// header; "-" from min on without a hit.  --stat-decimals D (0..9) keeps D fraction digits;
+// --stat-duration reads Go durations ("1m30.5s") and prints nanoseconds.
 //
 // MANIFEST has one line per container of the pod selection, in pod-spec order:
 //   <pod> TAB <init|container> TAB <container> TAB <path of the captured body | ->
@@ -93,6 +102,11 @@ void usage() {
                "                    the K most frequent messages of the selected lines, K in 1..65536, over all\n"
                "                    containers; with each run of digits counted as '#'; comparing the first N\n"
                "                    bytes of a message only; counted before --since / --tail apply)\n"
+               "                    [--stat KEY [--stat-decimals D | --stat-duration]]   (also writes\n"
+               "                    <logpath>/stats.tsv: per container and over all, the lines with the number\n"
+               "                    behind KEY (1..64 bytes), their min, max, sum, p50, p90, p99 and where the\n"
+               "                    maximum is; with D = 0..9 fraction digits kept; as Go durations, in ns;\n"
+               "                    counted before --since / --tail apply)\n"
                "                    [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST\n");
   std::exit(1);
 }
@@ -115,6 +129,9 @@ int main(int argc, char** argv) {
   bool merge = false, merge_ts = false;  // --merge, --merge-timestamps
   klf_groups_opts top{0, 0, 0, 0};
   bool top_set = false, top_mask = false, top_key_set = false;  // --top, --top-mask-digits, --top-key-bytes
+  std::string stat_key;
+  uint32_t stat_decimals = 0;
+  bool stat_set = false, stat_dec_set = false, stat_duration = false;  // --stat, --stat-decimals, --stat-duration
   auto number = [&](const std::string& v, unsigned long long max) -> uint32_t {
     char* end = nullptr;
     const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
@@ -152,6 +169,9 @@ int main(int argc, char** argv) {
     else if (a == "--top") { top.top = number(val(), KLF_GROUPS_MAX_TOP); top_set = true; }
     else if (a == "--top-mask-digits") top_mask = true;
     else if (a == "--top-key-bytes") { top.max_key = number(val(), 0xFFFFFFFFull); top_key_set = true; }
+    else if (a == "--stat") { stat_key = val(); stat_set = true; }
+    else if (a == "--stat-decimals") { stat_decimals = number(val(), 9); stat_dec_set = true; }
+    else if (a == "--stat-duration") stat_duration = true;
     else if (a == "--device") device = std::atoi(val().c_str());
     else if (a == "--no-color") color = false;
     else if (a == "--now") {
@@ -171,6 +191,9 @@ int main(int argc, char** argv) {
   if (merge_ts && !merge) usage();
   if ((top_set && top.top == 0) || ((top_mask || top_key_set) && !top_set)) usage();
   if (top_mask) top.flags |= KLF_GROUPS_MASK_DIGITS;
+  if ((stat_set && (stat_key.empty() || stat_key.size() > KLF_FIELD_MAX_KEY)) || (stat_dec_set && stat_duration) ||
+      ((stat_dec_set || stat_duration) && !stat_set))
+    usage();
   // --from / --until: an instant, or a duration before `now` (--now may follow them)
   klf_window_opts window{{KLF_TIME_MIN_SEC, 0, 0}, {KLF_TIME_MAX_SEC, 0, 0},
                          regroup.before, regroup.after, regroup.flags, 0};
@@ -382,6 +405,48 @@ int main(int argc, char** argv) {
       }
       if (std::fclose(tf) != 0) panic_exit("close " + tpath);
       klf_groups_free(gr);
+    }
+    if (stat_set) {  // the field's statistics over the result that gets written, before it is
+      static const uint16_t quantiles[3] = {5000, 9000, 9900};  // p50, p90, p99
+      const klf_field_opts fo{(const uint8_t*)stat_key.data(), quantiles, (uint32_t)stat_key.size(), stat_decimals, 3,
+                              stat_duration ? KLF_FIELD_DURATION : 0u};
+      std::vector<klf_field_row> fr((size_t)n + 1);
+      std::vector<int64_t> fq(((size_t)n + 1) * 3);
+      rc = klf_result_field_stats(r, &fo, fr.data(), fq.data(), nullptr);
+      if (rc != KLF_OK) panic_exit(std::string("klf_result_field_stats: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      const std::string spath = logpath + "/stats.tsv";
+      FILE* sf = std::fopen(spath.c_str(), "w");
+      if (!sf) panic_exit("create " + spath);
+      auto fixed = [&](__int128 v) {  // a fixed-point value with stat_decimals fraction digits
+        if (v < 0) { std::fputc('-', sf); v = -v; }
+        __int128 scale = 1;
+        for (uint32_t k = 0; k < stat_decimals; ++k) scale *= 10;
+        char buf[48];
+        int len = 0;
+        __int128 ip = v / scale;
+        do { buf[len++] = (char)('0' + (int)(ip % 10)); ip /= 10; } while (ip);
+        while (len) std::fputc(buf[--len], sf);
+        if (stat_decimals) std::fprintf(sf, ".%0*llu", (int)stat_decimals, (unsigned long long)(v % scale));
+      };
+      for (uint32_t i = 0; i <= n; ++i) {
+        const klf_field_row& x = fr[i];
+        std::fprintf(sf, "%s\t%s\t%llu\t%llu\t%llu", i < n ? pods[table[i].pod].name.c_str() : "*",
+                     i < n ? cname[i].c_str() : "*", (unsigned long long)x.lines, (unsigned long long)x.hits,
+                     (unsigned long long)x.bad);
+        if (!x.hits || x.max_stream >= n) {
+          std::fprintf(sf, "\t-\t-\t-\t-\t-\t-\t-\n");
+          continue;
+        }
+        const __int128 sum = (__int128)x.sum_hi * ((__int128)1 << 64) + (__int128)x.sum_lo;
+        for (const __int128 v : {(__int128)x.min, (__int128)x.max, sum, (__int128)fq[3 * (size_t)i],
+                                 (__int128)fq[3 * (size_t)i + 1], (__int128)fq[3 * (size_t)i + 2]}) {
+          std::fputc('\t', sf);
+          fixed(v);
+        }
+        std::fprintf(sf, "\t%s/%s:%llu\n", pods[table[x.max_stream].pod].name.c_str(), cname[x.max_stream].c_str(),
+                     (unsigned long long)x.max_line + 1);
+      }
+      if (std::fclose(sf) != 0) panic_exit("close " + spath);
     }
     if (merge) {  // the timeline of the result that gets written, beside the per-container files
       std::string tags;

@@ -36,6 +36,10 @@ TIMELINE_MAX_TAG = 1024       # KLF_TIMELINE_MAX_TAG: bytes of one stream's tag 
 GROUPS_MASK_DIGITS = 1        # KLF_GROUPS_MASK_DIGITS: each run of ASCII digits in a key becomes one '#'
 GROUPS_MAX_TOP = 65536        # KLF_GROUPS_MAX_TOP: klf_groups_opts.top at most
 GROUPS_MAX_GROUPS = 1 << 26   # KLF_GROUPS_MAX_GROUPS: klf_groups_opts.max_groups at most
+FIELD_DURATION = 1            # KLF_FIELD_DURATION: the value is a Go duration, in nanoseconds
+FIELD_MAX_KEY = 64            # KLF_FIELD_MAX_KEY: klf_field_opts.key_len at most
+FIELD_MAX_QUANTILES = 16      # KLF_FIELD_MAX_QUANTILES: klf_field_opts.n_quantiles at most
+FIELD_HIT, FIELD_MISS, FIELD_BAD = 0, 1, 2  # KLF_FIELD_HIT / _MISS / _BAD: klf_field_value's classes
 
 MODE_NAMES = {0: "none", 1: "never", 2: "all", 3: "literal1", 4: "general"}
 
@@ -98,6 +102,23 @@ GROUP_ENTRY = np.dtype([("count", "<u8"), ("first_line", "<u8"), ("last_line", "
                         ("first_stream", "<u4"), ("last_stream", "<u4"), ("key_len", "<u4"), ("_pad", "<u4")])
 
 
+class _FieldOpts(C.Structure):
+    _fields_ = [("key", C.c_void_p), ("quantiles", C.c_void_p), ("key_len", C.c_uint32), ("decimals", C.c_uint32),
+                ("n_quantiles", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _FieldRow(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("hits", C.c_uint64), ("bad", C.c_uint64), ("min", C.c_int64),
+                ("max", C.c_int64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("min_line", C.c_uint64),
+                ("max_line", C.c_uint64), ("min_stream", C.c_uint32), ("max_stream", C.c_uint32)]
+
+
+# klf_field_row (80 bytes)
+FIELD_ROW = np.dtype([("lines", "<u8"), ("hits", "<u8"), ("bad", "<u8"), ("min", "<i8"), ("max", "<i8"),
+                      ("sum_lo", "<u8"), ("sum_hi", "<i8"), ("min_line", "<u8"), ("max_line", "<u8"),
+                      ("min_stream", "<u4"), ("max_stream", "<u4")])
+
+
 class _Counts(C.Structure):
     _fields_ = [("lines", C.c_uint64), ("parsed", C.c_uint64), ("since_ok", C.c_uint64),
                 ("matched", C.c_uint64), ("selected", C.c_uint64), ("out_bytes", C.c_uint64)]
@@ -155,6 +176,10 @@ SIGNATURES = {
     "klf_groups_free": (None, [C.c_void_p]),
     "klf_group_key": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                 C.POINTER(C.c_size_t)]),
+    "klf_result_field_stats": (C.c_int, [C.c_void_p, C.POINTER(_FieldOpts), C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_double)]),
+    "klf_field_value": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                  C.POINTER(C.c_int64)]),
     "klf_follow_open": (C.c_int, [C.c_void_p, C.POINTER(_Filter), C.POINTER(C.c_void_p)]),
     "klf_follow_feed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
     "klf_follow_flush": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -403,6 +428,21 @@ def group_key(content: bytes, max_key: int = 0, flags: int = 0) -> bytes:
     return out.raw[: n.value]
 
 
+def field_value(content: bytes, key: bytes, decimals: int = 0, duration: bool = False) -> Tuple[int, int]:
+    """klf_field_value: (class, value) of one content (without its '\\n') by SPEC.md S4f, from the
+    extractor the kernels run; class is FIELD_HIT, FIELD_MISS or FIELD_BAD (value 0 unless a hit).
+    No GPU."""
+    content, key = bytes(content), bytes(key)
+    src = C.create_string_buffer(content, len(content) or 1)
+    kb = C.create_string_buffer(key, len(key) or 1)
+    v = C.c_int64()
+    rc = _lib.klf_field_value(C.addressof(src), len(content), C.addressof(kb), len(key), int(decimals),
+                              FIELD_DURATION if duration else 0, C.byref(v))
+    if rc < 0:
+        _check(rc)
+    return rc, int(v.value)
+
+
 class Groups:
     """Grouped counts (klf_groups): `entries` is a numpy structured array (GROUP_ENTRY: count,
     first_line, last_line, key_off, first_stream, last_stream, key_len) in result order,
@@ -578,6 +618,33 @@ class Result:
         p = C.c_void_p()
         _check(_lib.klf_result_groups(self._p, C.byref(o), C.byref(p)), self._eng._h)
         return Groups(p.value, self._eng)
+
+    def field_stats(self, key: bytes, decimals: int = 0, duration: bool = False,
+                    quantiles: Sequence[int] = ()) -> Tuple[np.ndarray, np.ndarray]:
+        """klf_result_field_stats (SPEC.md S4f): over the lines of the set this result was
+        selected from (M, G' or G''; the parsed lines without patterns), before --since and
+        --tail, the statistics of the number behind the first `key` of each line: in units of
+        10^-decimals, or with `duration` a Go duration in nanoseconds.  quantiles: permyriad
+        values (0..10000), nearest rank.  Returns (rows, qvals): rows is a FIELD_ROW array of
+        n_streams + 1 rows (the last one over all streams), qvals an int64 array of shape
+        (n_streams + 1, len(quantiles)).  Read-only: this result stays the latest and valid.
+        The device time of the call (ms) is left in `self.field_ms`."""
+        key = bytes(key)
+        qs = np.array([int(q) for q in quantiles], dtype=np.int64)
+        if ((qs < 0) | (qs > 0xFFFF)).any():
+            raise ValueError("field_stats: quantiles are permyriad values")
+        q16 = qs.astype(np.uint16)
+        kb = C.create_string_buffer(key, len(key) or 1)
+        o = _FieldOpts(C.addressof(kb), q16.ctypes.data if len(q16) else None, len(key), int(decimals), len(q16),
+                       FIELD_DURATION if duration else 0)
+        rows = np.zeros(self.n_streams + 1, dtype=FIELD_ROW)
+        qvals = np.zeros((self.n_streams + 1, len(q16)), dtype=np.int64)
+        ms = C.c_double()
+        _check(_lib.klf_result_field_stats(self._p, C.byref(o), C.c_void_p(rows.ctypes.data),
+                                           C.c_void_p(qvals.ctypes.data) if len(q16) else None, C.byref(ms)),
+               self._eng._h)
+        self.field_ms = float(ms.value)
+        return rows, qvals
 
     def last_unparsed(self, i: int) -> int:
         """klf_result_last_unparsed: rank from the end (over newline-terminated lines) of the
