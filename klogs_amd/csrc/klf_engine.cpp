@@ -2292,6 +2292,132 @@ extern "C" int klf_result_pattern_counts(klf_result* r, uint32_t id, uint64_t* c
   return KLF_OK;
 }
 
+// ------------------------------------------ the scaffold of a call on a finished run ---
+
+namespace {
+// What a call (klf_result_histogram, _timeline, _groups, _field_stats) holds for its duration:
+// device buffers and the two events around its device time, given back on every return path.
+// `fn` is the calling function's name and `noun` what it makes, for the messages.
+struct CallScratch {
+  klf_engine* e;
+  const char *fn, *noun;
+  hipStream_t st;
+  std::vector<DevBuf> bufs;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  CallScratch(klf_engine* e_, const char* fn_, const char* noun_) : e(e_), fn(fn_), noun(noun_), st(e_->stream) {}
+  CallScratch(const CallScratch&) = delete;
+  ~CallScratch() {
+    for (DevBuf& b : bufs) b.release();
+    for (auto& x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  // any buffer: the call's own or one of the object it returns
+  int alloc(DevBuf& b, size_t bytes, const char* what) {
+    const hipError_t h = b.ensure(bytes);
+    if (h == hipSuccess) return KLF_OK;
+    (void)hipGetLastError();
+    if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string(fn) + ": alloc " + what);
+    return hip_err(e, h, what);
+  }
+  // a buffer of the call
+  template <class T>
+  int alloc(T*& p, size_t bytes, const char* what) {
+    DevBuf b;
+    const int rc = alloc(b, bytes, what);
+    p = b.as<T>();
+    bufs.push_back(b);
+    return rc;
+  }
+  std::string msg(const char* a, const char* b = "") const { return std::string(a) + noun + b; }
+  // The device time: start() before the first launch, then finish() after the last one, or
+  // stop() there and elapsed() behind a sync of the caller's own.
+  int start() {
+    for (auto& x : ev) HIPCHK(e, hipEventCreate(&x), msg("", " events").c_str());
+    HIPCHK(e, hipEventRecord(ev[0], st), msg("record ", " start").c_str());
+    return KLF_OK;
+  }
+  int stop() {
+    HIPCHK(e, hipEventRecord(ev[1], st), msg("record ", " end").c_str());
+    return KLF_OK;
+  }
+  int elapsed(double& ms) {
+    float f = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&f, ev[0], ev[1]), msg("", " timing").c_str());
+    ms = f;
+    return KLF_OK;
+  }
+  int finish(double& ms) {
+    if (int rc = stop()) return rc;
+    HIPCHK(e, hipStreamSynchronize(st), msg("sync ").c_str());
+    return elapsed(ms);
+  }
+};
+
+// The sort of n TlItems by their key (klf_kernels.hpp, SortArgs) as the host drives it:
+// prepare(n), the caller's kernel fills s.items[0], digits() makes the digit histograms and
+// reads them back (one copy, one sync), passes(p0, p1) runs the passes over the digits p0 ..
+// p1 - 1 that differ somewhere (one bin holding all n: nothing to move); sorted() is the buffer
+// the last pass wrote.  With n = 0 nothing is allocated, launched or read back.
+struct DeviceSort {
+  CallScratch& sc;
+  klf::SortArgs s{};
+  uint32_t cur = 0;
+  std::vector<uint64_t> dh;
+  explicit DeviceSort(CallScratch& sc_) : sc(sc_) {}
+  int prepare(uint64_t n) {
+    s.n = n;
+    if (!n) return KLF_OK;
+    for (auto& it : s.items)
+      if (int rc = sc.alloc(it, (size_t)n * sizeof(klf::TlItem), "sort items")) return rc;
+    return sc.alloc(s.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms");
+  }
+  int digits() {
+    if (!s.n) return KLF_OK;
+    dh.resize((size_t)klf::kTlDigits * 256);
+    HIPCHK(sc.e, klf::launch_sort_digits(s, sc.st, sc.e->num_cus), "launch k_tl_digits");
+    HIPCHK(sc.e, hipMemcpyAsync(dh.data(), s.dhist, dh.size() * 8, hipMemcpyDeviceToHost, sc.st), "D2H digit histograms");
+    HIPCHK(sc.e, hipStreamSynchronize(sc.st), "sync digit histograms");
+    return KLF_OK;
+  }
+  int passes(uint32_t p0, uint32_t p1) {
+    for (uint32_t p = p0; p < p1 && s.n; ++p) {
+      bool one_bin = false;
+      for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == s.n;
+      if (one_bin) continue;
+      if (!s.bcnt) {
+        const size_t nblocks = (size_t)((s.n + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
+        if (int rc = sc.alloc(s.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
+      }
+      HIPCHK(sc.e, klf::launch_sort_pass(s, p, cur, sc.st), "launch radix pass");
+      cur ^= 1u;
+    }
+    return KLF_OK;
+  }
+  klf::TlItem* sorted() const { return s.items[cur]; }
+};
+}  // namespace
+
+// Segment -> stream id.
+static std::vector<uint32_t> seg_streams(const klf_result* r) {
+  std::vector<uint32_t> v(r->so.size(), 0u);
+  for (uint32_t id = 0; id < r->n_streams; ++id)
+    if (r->seg_of[id] >= 0) v[(size_t)r->seg_of[id]] = id;
+  return v;
+}
+
+// The host copy of the n elements at d that a view of a returned object hands out: made by the
+// first call that asks, kept until the object is freed.
+template <class T>
+static int host_view(klf_engine* e, std::vector<T>& v, bool& have, const DevBuf& d, uint64_t n, const char* what) {
+  if (!have && n) {
+    try { v.resize((size_t)n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
+    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
+    HIPCHK(e, hipMemcpy(v.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost), what);
+  }
+  have = true;
+  return KLF_OK;
+}
+
 extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint64_t* counts, uint64_t* outside,
                                     double* ms) {
   if (!r || !o || !counts) return KLF_EINVAL;
@@ -2332,15 +2458,14 @@ extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint6
   HIPCHK(e, e->d_thist.ensure(tbytes), "alloc histogram table");
   HIPCHK(e, e->h_thist.ensure(tbytes), "alloc histogram readback");
   g.table = e->d_thist.as<uint64_t>();
-  // (ev[0] / ev[5] bracket a run or a re-tail, whose result read them when it was made)
-  HIPCHK(e, klf::launch_hist(g, e->stream, e->ev[0], e->ev[5], e->num_cus), "launch k_hist");
+  CallScratch sc(e, "klf_result_histogram", "histogram");  // (its events alone: the table is the engine's)
+  if (int rc = sc.start()) return rc;
+  HIPCHK(e, klf::launch_hist(g, e->stream, e->num_cus), "launch k_hist");
+  if (int rc = sc.stop()) return rc;
   HIPCHK(e, hipMemcpyAsync(e->h_thist.p, e->d_thist.p, tbytes, hipMemcpyDeviceToHost, e->stream), "D2H histogram");
   HIPCHK(e, hipStreamSynchronize(e->stream), "sync histogram");
-  if (ms) {
-    float f = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&f, e->ev[0], e->ev[5]), "histogram timing");
-    *ms = f;
-  }
+  if (ms)
+    if (int rc = sc.elapsed(*ms)) return rc;
   const uint64_t* tab = e->h_thist.as<uint64_t>();
   for (uint32_t id = 0; id < r->n_streams; ++id) {
     const int64_t s = r->seg_of[id];
@@ -2371,29 +2496,6 @@ struct klf_timeline {
 static_assert(sizeof(klf_timeline_entry) == sizeof(klf::TlEntry) && sizeof(klf_timeline_entry) == 32,
               "klf_timeline_entry is the kernels' TlEntry");
 
-namespace {
-// The call's scratch: the chunk bases, both item buffers, the side records, the histograms, the
-// block counts and sums, the tag tables; freed when klf_result_timeline returns.
-struct TlScratch {
-  DevBuf cbase, items[2], side, dhist, bcnt, psum, segtab, tags;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~TlScratch() {
-    for (DevBuf* b : {&cbase, &items[0], &items[1], &side, &dhist, &bcnt, &psum, &segtab, &tags}) b->release();
-    for (auto& x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-}  // namespace
-
-static int tl_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
-  const hipError_t h = b.ensure(bytes);
-  if (h == hipSuccess) return KLF_OK;
-  (void)hipGetLastError();
-  if (h == hipErrorOutOfMemory)
-    return set_err(e, KLF_ENOMEM, std::string("klf_result_timeline: alloc ") + what);
-  return hip_err(e, h, what);
-}
-
 extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, klf_timeline** out) {
   if (!r || !o || !out) return KLF_EINVAL;
   klf_engine* e = r->e;
@@ -2418,95 +2520,66 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   hipStream_t st = e->stream;
-  TlScratch sc;
+  CallScratch sc(e, "klf_result_timeline", "timeline");
   klf::TlArgs g{};
   g.v = sel_view(r);
   g.timestamps = (o->flags & KLF_TIMELINE_TIMESTAMPS) ? 1u : 0u;
   // per segment: its stream id and its tag
+  const std::vector<uint32_t> streams = seg_streams(r);
   std::vector<uint32_t> segtab((size_t)nsegs * 3, 0u);
-  for (uint32_t id = 0; id < r->n_streams; ++id) {
-    const int64_t s = r->seg_of[id];
-    if (s < 0) continue;
-    segtab[3 * (size_t)s] = id;
+  for (uint32_t s = 0; s < nsegs; ++s) {
+    const uint32_t id = segtab[3 * (size_t)s] = streams[s];
     if (o->tags) {
       segtab[3 * (size_t)s + 1] = o->tag_off[id];
       segtab[3 * (size_t)s + 2] = o->tag_off[id + 1] - o->tag_off[id];
     }
   }
   const uint32_t tag_bytes = o->tags ? o->tag_off[r->n_streams] : 0u;
-  if (int rc = tl_alloc(e, sc.segtab, segtab.size() * 4, "segment table")) return rc;
-  HIPCHK(e, hipMemcpyAsync(sc.segtab.p, segtab.data(), segtab.size() * 4, hipMemcpyHostToDevice, st), "H2D segment table");
-  g.segtab = sc.segtab.as<uint32_t>();
+  uint32_t* d_segtab = nullptr;
+  if (int rc = sc.alloc(d_segtab, segtab.size() * 4, "segment table")) return rc;
+  HIPCHK(e, hipMemcpyAsync(d_segtab, segtab.data(), segtab.size() * 4, hipMemcpyHostToDevice, st), "H2D segment table");
+  g.segtab = d_segtab;
   if (tag_bytes) {
-    if (int rc = tl_alloc(e, sc.tags, tag_bytes, "tags")) return rc;
-    HIPCHK(e, hipMemcpyAsync(sc.tags.p, o->tags, tag_bytes, hipMemcpyHostToDevice, st), "H2D tags");
-    g.tags = sc.tags.as<uint8_t>();
+    uint8_t* d_tags = nullptr;
+    if (int rc = sc.alloc(d_tags, tag_bytes, "tags")) return rc;
+    HIPCHK(e, hipMemcpyAsync(d_tags, o->tags, tag_bytes, hipMemcpyHostToDevice, st), "H2D tags");
+    g.tags = d_tags;
   }
-  if (int rc = tl_alloc(e, sc.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
-  g.cbase = sc.cbase.as<uint64_t>();
-  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "timeline events");
-  auto finish = [&]() -> int {  // the device time, first launch to last
-    HIPCHK(e, hipEventRecord(sc.ev[1], st), "record timeline end");
-    HIPCHK(e, hipStreamSynchronize(st), "sync timeline");
-    float f = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "timeline timing");
-    t->ms = f;
-    return KLF_OK;
-  };
-  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record timeline start");
+  if (int rc = sc.alloc(g.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
+  if (int rc = sc.start()) return rc;
   // 1. E lines per chunk -> n
-  HIPCHK(e, klf::launch_tl_count(g, st, e->num_cus), "launch k_tl_count");
+  HIPCHK(e, klf::launch_tl_count(g.v, g.cbase, true, st, e->num_cus), "launch k_tl_count");
   uint64_t n = 0;
   HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H timeline size");
   HIPCHK(e, hipStreamSynchronize(st), "sync timeline size");
   if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_timeline: more than 2^32 - 1 entries");
   if (!n) {
-    if (int rc = finish()) return rc;
+    if (int rc = sc.finish(t->ms)) return rc;
     *out = t.release();
     return KLF_OK;
   }
   g.n = n;
-  // 2. keys and the digit histograms
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = tl_alloc(e, sc.items[k], n * sizeof(klf::TlItem), "sort items")) return rc;
-    g.items[k] = sc.items[k].as<klf::TlItem>();
-  }
-  if (int rc = tl_alloc(e, sc.side, n * sizeof(klf::TlSide), "side records")) return rc;
-  g.side = sc.side.as<klf::TlSide>();
-  if (int rc = tl_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
-  g.dhist = sc.dhist.as<uint64_t>();
+  // 2. keys, 3. the sort
+  DeviceSort sort(sc);
+  if (int rc = sort.prepare(n)) return rc;
+  for (int k = 0; k < 2; ++k) g.items[k] = sort.s.items[k];
+  if (int rc = sc.alloc(g.side, n * sizeof(klf::TlSide), "side records")) return rc;
   HIPCHK(e, klf::launch_tl_keys(g, st, e->num_cus), "launch k_tl_keys");
-  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
-  HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
-  HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
-  // 3. the passes whose digit differs somewhere (one bin holding all n: nothing to move)
-  const size_t nblocks = (size_t)((n + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
-  uint32_t cur = 0;
-  for (uint32_t p = 0; p < klf::kTlDigits; ++p) {
-    bool one_bin = false;
-    for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n;
-    if (one_bin) continue;
-    if (!g.bcnt) {
-      if (int rc = tl_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
-      g.bcnt = sc.bcnt.as<uint32_t>();
-    }
-    HIPCHK(e, klf::launch_tl_pass(g, p, cur, st), "launch radix pass");
-    cur ^= 1u;
-  }
+  if (int rc = sort.digits()) return rc;
+  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
   // 4. rendered lengths -> offsets, entries, bytes
   const size_t pblocks = (size_t)((n + klf::kTlPlanBlock - 1) / klf::kTlPlanBlock);
-  if (int rc = tl_alloc(e, sc.psum, (pblocks + 1) * 8, "block sums")) return rc;
-  g.psum = sc.psum.as<uint64_t>();
-  HIPCHK(e, klf::launch_tl_plan(g, cur, st), "launch k_tl_plan");
+  if (int rc = sc.alloc(g.psum, (pblocks + 1) * 8, "block sums")) return rc;
+  HIPCHK(e, klf::launch_tl_plan(g, sort.cur, st), "launch k_tl_plan");
   uint64_t total = 0;
   HIPCHK(e, hipMemcpyAsync(&total, g.psum + pblocks, 8, hipMemcpyDeviceToHost, st), "D2H merged length");
   HIPCHK(e, hipStreamSynchronize(st), "sync merged length");
-  if (int rc = tl_alloc(e, t->d_entries, n * sizeof(klf::TlEntry), "entries")) return rc;
-  if (int rc = tl_alloc(e, t->d_bytes, total + 16, "merged bytes")) return rc;
+  if (int rc = sc.alloc(t->d_entries, n * sizeof(klf::TlEntry), "entries")) return rc;
+  if (int rc = sc.alloc(t->d_bytes, total + 16, "merged bytes")) return rc;
   g.entries = t->d_entries.as<klf::TlEntry>();
   g.out = t->d_bytes.as<uint8_t>();
-  HIPCHK(e, klf::launch_tl_copy(g, cur, st), "launch k_tl_copy");
-  if (int rc = finish()) return rc;
+  HIPCHK(e, klf::launch_tl_copy(g, sort.cur, st), "launch k_tl_copy");
+  if (int rc = sc.finish(t->ms)) return rc;
   t->n = n;
   t->len = total;
   *out = t.release();
@@ -2515,14 +2588,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
 
 extern "C" int klf_timeline_entries(klf_timeline* t, const klf_timeline_entry** ent, uint64_t* n) {
   if (!t || !ent || !n) return KLF_EINVAL;
-  klf_engine* e = t->e;
-  if (!t->have_entries && t->n) {
-    try { t->entries.resize((size_t)t->n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
-    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-    HIPCHK(e, hipMemcpy(t->entries.data(), t->d_entries.p, (size_t)t->n * sizeof(klf_timeline_entry), hipMemcpyDeviceToHost),
-           "D2H timeline entries");
-  }
-  t->have_entries = true;
+  if (int rc = host_view(t->e, t->entries, t->have_entries, t->d_entries, t->n, "D2H timeline entries")) return rc;
   *ent = t->entries.data();
   *n = t->n;
   return KLF_OK;
@@ -2532,13 +2598,7 @@ extern "C" int klf_timeline_bytes(klf_timeline* t, const uint8_t** bytes, uint64
   if (!t || !len) return KLF_EINVAL;
   *len = t->len;
   if (!bytes) return KLF_OK;
-  klf_engine* e = t->e;
-  if (!t->have_bytes && t->len) {
-    try { t->bytes.resize((size_t)t->len); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
-    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-    HIPCHK(e, hipMemcpy(t->bytes.data(), t->d_bytes.p, (size_t)t->len, hipMemcpyDeviceToHost), "D2H merged bytes");
-  }
-  t->have_bytes = true;
+  if (int rc = host_view(t->e, t->bytes, t->have_bytes, t->d_bytes, t->len, "D2H merged bytes")) return rc;
   *bytes = t->bytes.data();
   return KLF_OK;
 }
@@ -2613,29 +2673,6 @@ static_assert(sizeof(klf_group_entry) == sizeof(klf::GrEntry) && sizeof(klf_grou
               "klf_group_entry is the kernels' GrEntry");
 static_assert(KLF_GROUPS_MASK_DIGITS == klf::kGroupsMaskDigits, "one flag value for the host helper and the kernels");
 
-namespace {
-// The call's scratch: the hash table, the occupied-slot sums, the sort's items, the slot of each
-// item, the histograms, the block counts, the key lengths, the segment -> stream table; freed
-// when klf_result_groups returns.
-struct GrScratch {
-  DevBuf table, bsum, items[2], gslot, dhist, bcnt, klen, segstream;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~GrScratch() {
-    for (DevBuf* b : {&table, &bsum, &items[0], &items[1], &gslot, &dhist, &bcnt, &klen, &segstream}) b->release();
-    for (auto& x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-}  // namespace
-
-static int gr_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
-  const hipError_t h = b.ensure(bytes);
-  if (h == hipSuccess) return KLF_OK;
-  (void)hipGetLastError();
-  if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string("klf_result_groups: alloc ") + what);
-  return hip_err(e, h, what);
-}
-
 // KLF_GROUPS_HASH_BITS (1..64, a test hook: DESIGN.md): the low bits of the hash that are used.
 static uint32_t groups_hash_bits() {
   const char* s = getenv("KLF_GROUPS_HASH_BITS");
@@ -2667,7 +2704,7 @@ extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_gr
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   hipStream_t st = e->stream;
-  GrScratch sc;
+  CallScratch sc(e, "klf_result_groups", "groups");
   klf::GroupArgs g{};
   g.v = sel_view(r);
   g.max_key = o->max_key;
@@ -2680,20 +2717,9 @@ extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_gr
   while ((1ull << g.table_log2) < 2 * hold) ++g.table_log2;  // (<= 27)
   const uint64_t P = 1ull << g.table_log2;
   const size_t cblocks = (size_t)((P + klf::kGrCountBlock - 1) / klf::kGrCountBlock);
-  if (int rc = gr_alloc(e, sc.table, (size_t)(4 * P + 2) * 8, "hash table")) return rc;
-  if (int rc = gr_alloc(e, sc.bsum, (cblocks + 1) * 8, "slot sums")) return rc;
-  g.table = sc.table.as<uint64_t>();
-  g.bsum = sc.bsum.as<uint64_t>();
-  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "groups events");
-  auto finish = [&]() -> int {  // the device time, first launch to last
-    HIPCHK(e, hipEventRecord(sc.ev[1], st), "record groups end");
-    HIPCHK(e, hipStreamSynchronize(st), "sync groups");
-    float f = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "groups timing");
-    t->ms = f;
-    return KLF_OK;
-  };
-  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record groups start");
+  if (int rc = sc.alloc(g.table, (size_t)(4 * P + 2) * 8, "hash table")) return rc;
+  if (int rc = sc.alloc(g.bsum, (cblocks + 1) * 8, "slot sums")) return rc;
+  if (int rc = sc.start()) return rc;
   // 1. every line of H into the table; the occupied slots -> n_groups
   HIPCHK(e, klf::launch_gr_insert(g, st, e->num_cus), "launch k_gr_insert");
   HIPCHK(e, klf::launch_gr_count(g, st), "launch k_gr_count");
@@ -2708,60 +2734,37 @@ extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_gr
   t->n_lines = stats[0];
   t->n_groups = n_groups;
   if (!n_groups) {
-    if (int rc = finish()) return rc;
+    if (int rc = sc.finish(t->ms)) return rc;
     *out = t.release();
     return KLF_OK;
   }
-  // 2. one item per group, sorted by (count desc, first asc) with the timeline's passes
+  // 2. one item per group, sorted by (count desc, first asc)
   g.n_groups = n_groups;
-  klf::TlArgs tg{};
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = gr_alloc(e, sc.items[k], n_groups * sizeof(klf::TlItem), "sort items")) return rc;
-    tg.items[k] = sc.items[k].as<klf::TlItem>();
-  }
-  if (int rc = gr_alloc(e, sc.gslot, n_groups * 4, "item slots")) return rc;
-  if (int rc = gr_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
-  g.items = tg.items[0];
-  g.gslot = sc.gslot.as<uint32_t>();
-  g.dhist = tg.dhist = sc.dhist.as<uint64_t>();
-  tg.n = n_groups;
-  HIPCHK(e, klf::launch_gr_fill(g, st, e->num_cus), "launch k_gr_fill");
-  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
-  HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
-  HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
-  const size_t nblocks = (size_t)((n_groups + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
-  uint32_t cur = 0;
-  for (uint32_t p = 0; p < klf::kTlDigits; ++p) {
-    bool one_bin = false;
-    for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n_groups;
-    if (one_bin) continue;
-    if (!tg.bcnt) {
-      if (int rc = gr_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
-      tg.bcnt = sc.bcnt.as<uint32_t>();
-    }
-    HIPCHK(e, klf::launch_tl_pass(tg, p, cur, st), "launch radix pass");
-    cur ^= 1u;
-  }
+  DeviceSort sort(sc);
+  if (int rc = sort.prepare(n_groups)) return rc;
+  g.items = sort.s.items[0];
+  if (int rc = sc.alloc(g.gslot, n_groups * 4, "item slots")) return rc;
+  HIPCHK(e, klf::launch_gr_fill(g, st), "launch k_gr_fill");
+  if (int rc = sort.digits()) return rc;
+  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
   // 3. the first `top` groups: key lengths -> offsets, then the records and the key bytes
   g.top = (uint32_t)std::min<uint64_t>(o->top, n_groups);
-  std::vector<uint32_t> segstream(nsegs, 0u);
-  for (uint32_t id = 0; id < r->n_streams; ++id)
-    if (r->seg_of[id] >= 0) segstream[(size_t)r->seg_of[id]] = id;
-  if (int rc = gr_alloc(e, sc.segstream, (size_t)nsegs * 4, "segment table")) return rc;
-  HIPCHK(e, hipMemcpyAsync(sc.segstream.p, segstream.data(), (size_t)nsegs * 4, hipMemcpyHostToDevice, st), "H2D segment table");
-  g.segstream = sc.segstream.as<uint32_t>();
-  if (int rc = gr_alloc(e, sc.klen, ((size_t)g.top + 1) * 8, "key lengths")) return rc;
-  g.klen = sc.klen.as<uint64_t>();
-  HIPCHK(e, klf::launch_gr_plan(g, tg.items[cur], st), "launch k_gr_plan");
+  const std::vector<uint32_t> segstream = seg_streams(r);
+  uint32_t* d_segstream = nullptr;
+  if (int rc = sc.alloc(d_segstream, (size_t)nsegs * 4, "segment table")) return rc;
+  HIPCHK(e, hipMemcpyAsync(d_segstream, segstream.data(), (size_t)nsegs * 4, hipMemcpyHostToDevice, st), "H2D segment table");
+  g.segstream = d_segstream;
+  if (int rc = sc.alloc(g.klen, ((size_t)g.top + 1) * 8, "key lengths")) return rc;
+  HIPCHK(e, klf::launch_gr_plan(g, sort.sorted(), st), "launch k_gr_plan");
   uint64_t total = 0;
   HIPCHK(e, hipMemcpyAsync(&total, g.klen + g.top, 8, hipMemcpyDeviceToHost, st), "D2H key bytes");
   HIPCHK(e, hipStreamSynchronize(st), "sync key bytes");
-  if (int rc = gr_alloc(e, t->d_entries, (size_t)g.top * sizeof(klf::GrEntry), "entries")) return rc;
-  if (int rc = gr_alloc(e, t->d_keys, total + 16, "key bytes")) return rc;
+  if (int rc = sc.alloc(t->d_entries, (size_t)g.top * sizeof(klf::GrEntry), "entries")) return rc;
+  if (int rc = sc.alloc(t->d_keys, total + 16, "key bytes")) return rc;
   g.entries = t->d_entries.as<klf::GrEntry>();
   g.keys = t->d_keys.as<uint8_t>();
-  HIPCHK(e, klf::launch_gr_render(g, tg.items[cur], st), "launch k_gr_render");
-  if (int rc = finish()) return rc;
+  HIPCHK(e, klf::launch_gr_render(g, sort.sorted(), st), "launch k_gr_render");
+  if (int rc = sc.finish(t->ms)) return rc;
   t->n = g.top;
   t->key_bytes = total;
   *out = t.release();
@@ -2770,14 +2773,7 @@ extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_gr
 
 extern "C" int klf_groups_entries(klf_groups* t, const klf_group_entry** ent, uint64_t* n) {
   if (!t || !ent || !n) return KLF_EINVAL;
-  klf_engine* e = t->e;
-  if (!t->have_entries && t->n) {
-    try { t->entries.resize((size_t)t->n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
-    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-    HIPCHK(e, hipMemcpy(t->entries.data(), t->d_entries.p, (size_t)t->n * sizeof(klf_group_entry), hipMemcpyDeviceToHost),
-           "D2H group entries");
-  }
-  t->have_entries = true;
+  if (int rc = host_view(t->e, t->entries, t->have_entries, t->d_entries, t->n, "D2H group entries")) return rc;
   *ent = t->entries.data();
   *n = t->n;
   return KLF_OK;
@@ -2785,13 +2781,7 @@ extern "C" int klf_groups_entries(klf_groups* t, const klf_group_entry** ent, ui
 
 extern "C" int klf_groups_keys(klf_groups* t, const uint8_t** bytes, uint64_t* len) {
   if (!t || !bytes || !len) return KLF_EINVAL;
-  klf_engine* e = t->e;
-  if (!t->have_keys && t->key_bytes) {
-    try { t->keys.resize((size_t)t->key_bytes); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
-    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-    HIPCHK(e, hipMemcpy(t->keys.data(), t->d_keys.p, (size_t)t->key_bytes, hipMemcpyDeviceToHost), "D2H group keys");
-  }
-  t->have_keys = true;
+  if (int rc = host_view(t->e, t->keys, t->have_keys, t->d_keys, t->key_bytes, "D2H group keys")) return rc;
   *bytes = t->keys.data();
   *len = t->key_bytes;
   return KLF_OK;
@@ -2842,30 +2832,6 @@ static_assert(KLF_FIELD_DURATION == klf::kFieldDuration && KLF_FIELD_MAX_KEY == 
                   KLF_FIELD_HIT == klf::kFieldHit && KLF_FIELD_MISS == klf::kFieldMiss && KLF_FIELD_BAD == klf::kFieldBad,
               "one set of values for the host helper and the kernels");
 
-namespace {
-// The call's scratch: the chunk bases of the lines and of the hits, the per-line values and
-// classes, both item buffers, the histograms, the block counts, and the result block (the
-// per-segment table, the segments' hit prefix, the rows, the quantile values); freed when
-// klf_result_field_stats returns.
-struct FsScratch {
-  DevBuf cbase, hbase, val, cs, items[2], dhist, bcnt, res;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~FsScratch() {
-    for (DevBuf* b : {&cbase, &hbase, &val, &cs, &items[0], &items[1], &dhist, &bcnt, &res}) b->release();
-    for (auto& x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-}  // namespace
-
-static int fs_alloc(klf_engine* e, DevBuf& b, size_t bytes, const char* what) {
-  const hipError_t h = b.ensure(bytes);
-  if (h == hipSuccess) return KLF_OK;
-  (void)hipGetLastError();
-  if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string("klf_result_field_stats: alloc ") + what);
-  return hip_err(e, h, what);
-}
-
 static bool field_opts_ok(const uint8_t* key, uint32_t key_len, uint32_t decimals, uint32_t flags) {
   return key && key_len >= 1 && key_len <= KLF_FIELD_MAX_KEY && !(flags & ~KLF_FIELD_DURATION) && decimals <= 9 &&
          !((flags & KLF_FIELD_DURATION) && decimals);
@@ -2896,7 +2862,7 @@ extern "C" int klf_result_field_stats(klf_result* r, const klf_field_opts* o, kl
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   hipStream_t st = e->stream;
-  FsScratch sc;
+  CallScratch sc(e, "klf_result_field_stats", "field statistics");
   klf::FieldArgs g{};
   g.v = sel_view(r);
   memcpy(g.key, o->key, o->key_len);
@@ -2905,89 +2871,50 @@ extern "C" int klf_result_field_stats(klf_result* r, const klf_field_opts* o, kl
   g.flags = o->flags;
   g.n_q = nq;
   for (uint32_t k = 0; k < nq; ++k) g.q[k] = o->quantiles[k];
-  if (int rc = fs_alloc(e, sc.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
-  if (int rc = fs_alloc(e, sc.hbase, (g.v.nchunks + 1) * 8, "chunk hit bases")) return rc;
-  g.cbase = sc.cbase.as<uint64_t>();
-  g.hbase = sc.hbase.as<uint64_t>();
+  if (int rc = sc.alloc(g.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
+  if (int rc = sc.alloc(g.hbase, (g.v.nchunks + 1) * 8, "chunk hit bases")) return rc;
   // the result block: the table, the segments' hit prefix, the rows, the quantile values
   const size_t tab_w = (size_t)klf::kFsTabRows * nsegs, hpre_w = (size_t)nsegs + 1,
                rows_w = ((size_t)nsegs + 1) * (sizeof(klf::FsRow) / 8), qv_w = ((size_t)nsegs + 1) * nq;
   const size_t res_w = tab_w + hpre_w + rows_w + qv_w;
-  if (int rc = fs_alloc(e, sc.res, res_w * 8, "result block")) return rc;
-  g.tab = sc.res.as<uint64_t>();
+  if (int rc = sc.alloc(g.tab, res_w * 8, "result block")) return rc;
   g.hpre = g.tab + tab_w;
   g.rows = reinterpret_cast<klf::FsRow*>(g.hpre + hpre_w);
   g.qv = reinterpret_cast<int64_t*>(g.hpre + hpre_w + rows_w);
-  for (auto& x : sc.ev) HIPCHK(e, hipEventCreate(&x), "field statistics events");
-  HIPCHK(e, hipEventRecord(sc.ev[0], st), "record field statistics start");
+  if (int rc = sc.start()) return rc;
   // 1. H lines per chunk -> n
-  HIPCHK(e, klf::launch_fs_count(g, st, e->num_cus), "launch k_fs_count");
+  HIPCHK(e, klf::launch_tl_count(g.v, g.cbase, false, st, e->num_cus), "launch k_tl_count");
   uint64_t n = 0;
   HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics size");
   HIPCHK(e, hipStreamSynchronize(st), "sync field statistics size");
   if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_field_stats: 2^32 or more lines in the selection");
   g.n = n;
   // 2. every line's class and value; per segment the counts and the sum; the hits per chunk -> n_hits
-  if (int rc = fs_alloc(e, sc.val, (size_t)n * 8, "values")) return rc;
-  if (int rc = fs_alloc(e, sc.cs, (size_t)n * 4, "classes")) return rc;
-  g.val = sc.val.as<int64_t>();
-  g.cs = sc.cs.as<uint32_t>();
+  if (int rc = sc.alloc(g.val, (size_t)n * 8, "values")) return rc;
+  if (int rc = sc.alloc(g.cs, (size_t)n * 4, "classes")) return rc;
   HIPCHK(e, klf::launch_fs_extract(g, st, e->num_cus), "launch k_fs_extract");
   uint64_t n_hits = 0;
   HIPCHK(e, hipMemcpyAsync(&n_hits, g.hbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics hits");
   HIPCHK(e, hipStreamSynchronize(st), "sync field statistics hits");
   g.n_hits = n_hits;
   // 3. the hits as sort items; value order -> the all-streams row; (segment, value) order -> the rest
-  klf::TlArgs tg{};
-  tg.n = n_hits;
-  uint32_t cur = 0;
-  if (n_hits) {
-    for (int k = 0; k < 2; ++k) {
-      if (int rc = fs_alloc(e, sc.items[k], (size_t)n_hits * sizeof(klf::TlItem), "sort items")) return rc;
-      tg.items[k] = sc.items[k].as<klf::TlItem>();
-    }
-    if (int rc = fs_alloc(e, sc.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms")) return rc;
-    g.items = tg.items[0];
-    g.dhist = tg.dhist = sc.dhist.as<uint64_t>();
-    HIPCHK(e, klf::launch_fs_compact(g, st, e->num_cus), "launch k_fs_compact");
-  }
-  std::vector<uint64_t> dh((size_t)klf::kTlDigits * 256);
-  if (n_hits) {
-    HIPCHK(e, hipMemcpyAsync(dh.data(), g.dhist, dh.size() * 8, hipMemcpyDeviceToHost, st), "D2H digit histograms");
-    HIPCHK(e, hipStreamSynchronize(st), "sync digit histograms");
-  }
-  const size_t nblocks = (size_t)((n_hits + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
-  auto passes = [&](uint32_t p0, uint32_t p1) -> int {  // the passes whose digit differs somewhere
-    for (uint32_t p = p0; p < p1 && n_hits; ++p) {
-      bool one_bin = false;
-      for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == n_hits;
-      if (one_bin) continue;
-      if (!tg.bcnt) {
-        if (int rc = fs_alloc(e, sc.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
-        tg.bcnt = sc.bcnt.as<uint32_t>();
-      }
-      HIPCHK(e, klf::launch_tl_pass(tg, p, cur, st), "launch radix pass");
-      cur ^= 1u;
-    }
-    return KLF_OK;
-  };
-  if (int rc = passes(0, 8)) return rc;
-  HIPCHK(e, klf::launch_fs_rows(g, tg.items[cur], 1u, st), "launch k_fs_rows");
-  if (int rc = passes(8, klf::kTlDigits)) return rc;
-  HIPCHK(e, klf::launch_fs_rows(g, tg.items[cur], 0u, st), "launch k_fs_rows");
+  DeviceSort sort(sc);
+  if (int rc = sort.prepare(n_hits)) return rc;
+  g.items = sort.s.items[0];
+  HIPCHK(e, klf::launch_fs_compact(g, st, e->num_cus), "launch k_fs_compact");  // (nothing with n_hits = 0)
+  if (int rc = sort.digits()) return rc;
+  if (int rc = sort.passes(0, 8)) return rc;
+  HIPCHK(e, klf::launch_fs_rows(g, sort.sorted(), 1u, st), "launch k_fs_rows");
+  if (int rc = sort.passes(8, klf::kTlDigits)) return rc;
+  HIPCHK(e, klf::launch_fs_rows(g, sort.sorted(), 0u, st), "launch k_fs_rows");
   // 4. one copy of the result block; segments -> stream ids; the all-streams counts and sum
   std::vector<uint64_t> res(res_w);
-  HIPCHK(e, hipEventRecord(sc.ev[1], st), "record field statistics end");
+  if (int rc = sc.stop()) return rc;
   HIPCHK(e, hipMemcpyAsync(res.data(), g.tab, res_w * 8, hipMemcpyDeviceToHost, st), "D2H field statistics");
   HIPCHK(e, hipStreamSynchronize(st), "sync field statistics");
-  if (ms) {
-    float f = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&f, sc.ev[0], sc.ev[1]), "field statistics timing");
-    *ms = f;
-  }
-  std::vector<uint32_t> segstream(nsegs, 0u);
-  for (uint32_t id = 0; id < r->n_streams; ++id)
-    if (r->seg_of[id] >= 0) segstream[(size_t)r->seg_of[id]] = id;
+  if (ms)
+    if (int rc = sc.elapsed(*ms)) return rc;
+  const std::vector<uint32_t> segstream = seg_streams(r);
   const uint64_t* tab = res.data();
   const klf::FsRow* drows = reinterpret_cast<const klf::FsRow*>(res.data() + tab_w + hpre_w);
   const int64_t* dqv = reinterpret_cast<const int64_t*>(res.data() + tab_w + hpre_w + rows_w);

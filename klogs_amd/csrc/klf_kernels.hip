@@ -3332,32 +3332,34 @@ __global__ __launch_bounds__(256) void k_hist(HistArgs g) {
 
 // Word w of E (0 past the line count): the selection word, the tail windows of the streams the
 // word meets, then the parsed / since_ok flags (read only where something is left).
-__device__ __forceinline__ uint32_t tl_e_word(const TlArgs& g, uint64_t w, uint64_t L) {
+__device__ __forceinline__ uint32_t tl_e_word(const SelView& v, uint64_t w, uint64_t L) {
   const uint64_t l0 = w * 32;
   if (l0 >= L) return 0u;
   uint32_t x = word_range_mask(w, 0, L);
-  if (g.v.bits_in) x &= g.v.bits_in[w];
+  if (v.bits_in) x &= v.bits_in[w];
   if (!x) return 0u;
   const uint64_t l1 = l0 + 32 < L ? l0 + 32 : L;
   uint32_t win = 0;
-  for (uint32_t s = find_seg_by_line(g.v.segout, g.v.nsegs, l0); s < g.v.nsegs && g.v.segout[s].line_lo < l1; ++s)
-    win |= word_range_mask(w, g.v.segout[s].win_lo, g.v.segout[s].win_hi);
+  for (uint32_t s = find_seg_by_line(v.segout, v.nsegs, l0); s < v.nsegs && v.segout[s].line_lo < l1; ++s)
+    win |= word_range_mask(w, v.segout[s].win_lo, v.segout[s].win_hi);
   x &= win;
   if (!x) return 0u;
-  return x & meta_word<true>(g.v.meta, w, L);
+  return x & meta_word<true>(v.meta, w, L);
 }
 
-__global__ __launch_bounds__(256) void k_tl_count(TlArgs g) {
+// Per chunk the lines of E (EMITTED: the timeline) or of H (the field statistics).
+template <bool EMITTED>
+__global__ __launch_bounds__(256) void k_tl_count(SelView v, uint64_t* cbase) {
   __shared__ uint32_t s_w[4];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
-  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+  const uint64_t L = v.segout[v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t;
-    const uint32_t cnt = wave_sum((uint32_t)__popc(tl_e_word(g, w, L)));
+    const uint32_t cnt = wave_sum((uint32_t)__popc(EMITTED ? tl_e_word(v, w, L) : view_word(v, w, L)));
     __syncthreads();  // (the previous chunk's sums are read)
     if (lane == 0) s_w[wv] = cnt;
     __syncthreads();
-    if (t == 0) g.cbase[c] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (t == 0) cbase[c] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
   }
 }
 
@@ -3391,7 +3393,7 @@ __global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
   const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
   for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    const uint32_t total = walk_publish(ws, g.v, tl_e_word(g, w, L), l0);
+    const uint32_t total = walk_publish(ws, g.v, tl_e_word(g.v, w, L), l0);
     if (lane == 0) s_tot[wv] = total;
     __syncthreads();
     uint64_t base = g.cbase[c];
@@ -3903,20 +3905,6 @@ struct FsBytes {
     return (uint8_t)(k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8)));
   }
 };
-
-__global__ __launch_bounds__(256) void k_fs_count(FieldArgs g) {
-  __shared__ uint32_t s_w[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
-  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
-    const uint64_t w = c * (kMatchChunk / 32) + t;
-    const uint32_t cnt = wave_sum((uint32_t)__popc(view_word(g.v, w, L)));
-    __syncthreads();  // (the previous chunk's sums are read)
-    if (lane == 0) s_w[wv] = cnt;
-    __syncthreads();
-    if (t == 0) g.cbase[c] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  }
-}
 
 __device__ __forceinline__ void fs_add(uint64_t* p, uint64_t x) {
   if (x) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)x);
@@ -5976,47 +5964,48 @@ hipError_t launch_retail(const RunArgs& a, hipStream_t st, hipEvent_t* ev, int n
   return e;
 }
 
-hipError_t launch_hist(const HistArgs& g, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, int num_cus) {
-  hipError_t e = hipEventRecord(ev0, st);
-  if (e != hipSuccess) return e;
-  if ((e = hipMemsetAsync(g.table, 0, (size_t)g.v.nsegs * (g.n_buckets + 2) * 8, st)) != hipSuccess) return e;
-  if (g.v.nchunks) {
-    hipLaunchKernelGGL(k_hist, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipEventRecord(ev1, st);
+hipError_t launch_hist(const HistArgs& g, hipStream_t st, int num_cus) {
+  const hipError_t e = hipMemsetAsync(g.table, 0, (size_t)g.v.nsegs * (g.n_buckets + 2) * 8, st);
+  if (e != hipSuccess || !g.v.nchunks) return e;
+  hipLaunchKernelGGL(k_hist, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+  return hipGetLastError();
 }
 
-hipError_t launch_tl_count(const TlArgs& g, hipStream_t st, int num_cus) {
-  if (g.v.nchunks) {
-    hipLaunchKernelGGL(k_tl_count, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+hipError_t launch_tl_count(const SelView& v, uint64_t* cbase, bool emitted, hipStream_t st, int num_cus) {
+  if (v.nchunks) {
+    const dim3 grid(chunk_grid(v.nchunks, num_cus));
+    if (emitted) hipLaunchKernelGGL(k_tl_count<true>, grid, dim3(256), 0, st, v, cbase);
+    else hipLaunchKernelGGL(k_tl_count<false>, grid, dim3(256), 0, st, v, cbase);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.v.nchunks);
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, cbase, v.nchunks);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_digits(const SortArgs& s, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(s.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
+  if (e != hipSuccess || !s.n) return e;
+  const uint64_t nb = (s.n + 255) / 256, dmax = (uint64_t)num_cus * 8;
+  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, s.items[0], s.n, s.dhist);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_pass(const SortArgs& s, uint32_t digit, uint32_t from, hipStream_t st) {
+  const uint32_t nb = (uint32_t)((s.n + kTlSortBlock - 1) / kTlSortBlock);
+  if (!nb || digit >= kTlDigits) return hipSuccess;
+  hipError_t e;
+  hipLaunchKernelGGL(k_tl_bcount, dim3(nb), dim3(256), 0, st, s.items[from & 1], s.n, digit, s.bcnt, nb);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_bscan, dim3(256), dim3(256), 0, st, s.bcnt, nb, s.dhist + (size_t)digit * 256);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_tl_scatter, dim3(nb), dim3(256), 0, st, s.items[from & 1], s.items[(from & 1) ^ 1], s.n, digit,
+                     s.bcnt, nb);
   return hipGetLastError();
 }
 
 hipError_t launch_tl_keys(const TlArgs& g, hipStream_t st, int num_cus) {
-  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
-  if (e != hipSuccess) return e;
   if (!g.n || !g.v.nchunks) return hipSuccess;
   hipLaunchKernelGGL(k_tl_keys, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  const uint64_t nb = (g.n + 255) / 256, dmax = (uint64_t)num_cus * 8;
-  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items[0], g.n, g.dhist);
-  return hipGetLastError();
-}
-
-hipError_t launch_tl_pass(const TlArgs& g, uint32_t digit, uint32_t from, hipStream_t st) {
-  const uint32_t nb = (uint32_t)((g.n + kTlSortBlock - 1) / kTlSortBlock);
-  if (!nb || digit >= kTlDigits) return hipSuccess;
-  hipError_t e;
-  hipLaunchKernelGGL(k_tl_bcount, dim3(nb), dim3(256), 0, st, g.items[from & 1], g.n, digit, g.bcnt, nb);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_tl_bscan, dim3(256), dim3(256), 0, st, g.bcnt, nb, g.dhist + (size_t)digit * 256);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_tl_scatter, dim3(nb), dim3(256), 0, st, g.items[from & 1], g.items[(from & 1) ^ 1], g.n, digit,
-                     g.bcnt, nb);
   return hipGetLastError();
 }
 
@@ -6056,13 +6045,9 @@ hipError_t launch_gr_count(const GroupArgs& g, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t st, int num_cus) {
-  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
-  if (e != hipSuccess || !g.n_groups) return e;
+hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t st) {
+  if (!g.n_groups) return hipSuccess;
   hipLaunchKernelGGL(k_gr_fill, dim3(gr_count_blocks(g)), dim3(256), 0, st, g);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  const uint64_t nb = (g.n_groups + 255) / 256, dmax = (uint64_t)num_cus * 8;
-  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items, g.n_groups, g.dhist);
   return hipGetLastError();
 }
 
@@ -6078,15 +6063,6 @@ hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t 
 hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_t st) {
   if (!g.top) return hipSuccess;
   hipLaunchKernelGGL(k_gr_render, dim3((g.top + 3) / 4), dim3(256), 0, st, g, sorted);
-  return hipGetLastError();
-}
-
-hipError_t launch_fs_count(const FieldArgs& g, hipStream_t st, int num_cus) {
-  if (g.v.nchunks) {
-    hipLaunchKernelGGL(k_fs_count, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.cbase, g.v.nchunks);
   return hipGetLastError();
 }
 
@@ -6108,12 +6084,8 @@ hipError_t launch_fs_extract(const FieldArgs& g, hipStream_t st, int num_cus) {
 }
 
 hipError_t launch_fs_compact(const FieldArgs& g, hipStream_t st, int num_cus) {
-  hipError_t e = hipMemsetAsync(g.dhist, 0, (size_t)kTlDigits * 256 * 8, st);
-  if (e != hipSuccess || !g.n_hits || !g.v.nchunks) return e;
+  if (!g.n_hits || !g.v.nchunks) return hipSuccess;
   hipLaunchKernelGGL(k_fs_compact, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  const uint64_t nb = (g.n_hits + 255) / 256, dmax = (uint64_t)num_cus * 8;
-  hipLaunchKernelGGL(k_tl_digits, dim3((uint32_t)(nb < dmax ? nb : dmax)), dim3(256), 0, st, g.items, g.n_hits, g.dhist);
   return hipGetLastError();
 }
 

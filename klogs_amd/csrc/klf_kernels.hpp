@@ -414,12 +414,10 @@ struct HistArgs {
 
 // Merged timeline of a finished run (klf_result_timeline, SPEC.md S4d): the emitted lines E of
 // all streams, sorted by (sec, nsec, stream, line) and rendered into one buffer.
-//   k_tl_count / k_tl_scan    E lines per kMatchChunk chunk, their exclusive prefix -> n
+//   k_tl_count<true> / k_tl_scan   E lines per kMatchChunk chunk, their exclusive prefix -> n
 //   k_tl_keys                 the selected-line walk over E: item[ord] = the line's instant, side[ord] =
 //                             its (line, segment); ord = its rank in (stream, line) order
-//   k_tl_digits               the twelve 256-bin histograms of the 96-bit key in one read
-//   k_tl_bcount / k_tl_bscan / k_tl_scatter   one stable LSD pass (8-bit digit) between the two
-//                             item buffers; the host skips a pass whose digit is the same in all
+//   the sort (SortArgs)       by the 96-bit key, stable
 //   k_tl_plan / k_tl_scan / k_tl_copy   rendered lengths per block of sorted positions, their
 //                             prefix, then the entry records and the gather copy
 // No kernel waits on another block: kernel boundaries are the only ordering.
@@ -442,27 +440,43 @@ static_assert(sizeof(TlItem) == 16 && sizeof(TlSide) == 16 && sizeof(TlEntry) ==
 constexpr uint32_t kTlDigits = 12;          // 8-bit digits of the key: nsec bytes 0..3, then sec_key bytes 0..7
 constexpr uint32_t kTlSortBlock = 2048;     // items per block of a radix pass (8 rounds of 256)
 constexpr uint32_t kTlPlanBlock = 256;      // sorted positions per block of the plan / copy
+
+// The sort of TlItems by their 96-bit key, stable (LSD radix, 8-bit digits), shared by the
+// timeline, the grouped counts and the field statistics; each fills items[0] with a kernel of
+// its own first.
+//   k_tl_digits               the twelve 256-bin histograms of the key in one read
+//   k_tl_bcount / k_tl_bscan / k_tl_scatter   one pass over a digit between the two item
+//                             buffers; the host skips a pass whose digit is the same in all
+struct SortArgs {
+  TlItem* items[2];         // [n] each: the ping-pong buffers
+  uint64_t n;
+  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_sort_digits)
+  uint32_t* bcnt;           // [256 * ceil(n / kTlSortBlock)] digit-major per-block counts, then offsets
+};
+// Zeroes s.dhist, then k_tl_digits over s.items[0].
+hipError_t launch_sort_digits(const SortArgs& s, hipStream_t stream, int num_cus);
+// One pass over digit `digit` from s.items[from] into s.items[from ^ 1].
+hipError_t launch_sort_pass(const SortArgs& s, uint32_t digit, uint32_t from, hipStream_t stream);
+
+// k_tl_count + k_tl_scan: per kMatchChunk chunk the lines of E (`emitted`) or of H (view_word)
+// into cbase[0 .. v.nchunks), then their exclusive prefix; cbase[v.nchunks] = the total.
+hipError_t launch_tl_count(const SelView& v, uint64_t* cbase, bool emitted, hipStream_t stream, int num_cus);
+
 struct TlArgs {
   SelView v;                // bits_in null: every line (no patterns)
   uint32_t timestamps;      // render the line's prefix too
   const uint32_t* segtab;   // [3 * nsegs] per segment: stream id, tag offset, tag length
   const uint8_t* tags;      // the tag bytes (null: no tags, every length 0)
   uint64_t* cbase;          // [nchunks + 1] E lines per chunk, then their exclusive prefix and n
-  uint64_t n;               // entries (known after k_tl_scan)
-  TlItem* items[2];         // [n] each: the ping-pong buffers of the sort
+  uint64_t n;               // entries (known after launch_tl_count)
+  TlItem* items[2];         // [n] each: the sort's buffers (k_tl_keys fills [0]; the plan and the copy read the sorted one)
   TlSide* side;             // [n]
-  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_tl_keys)
-  uint32_t* bcnt;           // [256 * ceil(n / kTlSortBlock)] digit-major per-block counts, then offsets
   uint64_t* psum;           // [ceil(n / kTlPlanBlock) + 1] rendered bytes per block, then prefix and total
   TlEntry* entries;         // [n]
   uint8_t* out;             // the merged bytes
 };
-// k_tl_count + k_tl_scan: g.cbase[g.nchunks] = n afterwards.
-hipError_t launch_tl_count(const TlArgs& g, hipStream_t stream, int num_cus);
-// k_tl_keys into g.items[0] / g.side, then g.dhist (k_tl_digits).
+// k_tl_keys into g.items[0] / g.side.
 hipError_t launch_tl_keys(const TlArgs& g, hipStream_t stream, int num_cus);
-// One radix pass over digit `digit` from g.items[from] into g.items[from ^ 1].
-hipError_t launch_tl_pass(const TlArgs& g, uint32_t digit, uint32_t from, hipStream_t stream);
 // k_tl_plan + k_tl_scan over the sorted g.items[which]: g.psum[blocks] = the merged length.
 hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t stream);
 // k_tl_copy: g.entries and g.out from the sorted g.items[which] and the scanned g.psum.
@@ -476,8 +490,8 @@ hipError_t launch_tl_copy(const TlArgs& g, uint32_t which, hipStream_t stream);
 //                             are settled by comparing the two keys byte for byte), then adds to
 //                             the slot's count / lowest line / highest line
 //   k_gr_count / k_tl_scan    occupied slots per kGrCountBlock slots, their prefix -> n_groups
-//   k_gr_fill / k_tl_digits   one TlItem per group: key = (~count, first), 80 bits of the 96
-//   launch_tl_pass            the timeline's stable LSD passes over those items
+//   k_gr_fill                 one TlItem per group: key = (~count, first), 80 bits of the 96
+//   the sort (SortArgs)       over those items
 //   k_gr_plan / k_tl_scan / k_gr_render   key lengths of the first `top` groups, their prefix,
 //                             then the entry records and the key bytes
 // No kernel waits on another thread: inside k_gr_insert a thread relies on the slot words alone
@@ -501,7 +515,6 @@ struct GroupArgs {
   uint64_t n_groups;        // (known after launch_gr_count)
   TlItem* items;            // [n_groups] the sort's input
   uint32_t* gslot;          // [n_groups] TlItem::ord -> slot
-  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_gr_fill)
   uint32_t top;             // groups rendered: min(opts.top, n_groups)
   uint64_t* klen;           // [top + 1] key lengths, then their prefix and the total
   const uint32_t* segstream;  // [nsegs] segment -> stream id
@@ -512,8 +525,8 @@ struct GroupArgs {
 hipError_t launch_gr_insert(const GroupArgs& g, hipStream_t stream, int num_cus);
 // k_gr_count + k_tl_scan: g.bsum[blocks] = n_groups afterwards.
 hipError_t launch_gr_count(const GroupArgs& g, hipStream_t stream);
-// k_gr_fill into g.items / g.gslot, then g.dhist (k_tl_digits).
-hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t stream, int num_cus);
+// k_gr_fill into g.items / g.gslot.
+hipError_t launch_gr_fill(const GroupArgs& g, hipStream_t stream);
 // k_gr_plan + k_tl_scan over the first g.top of `sorted`: g.klen[g.top] = the key bytes.
 hipError_t launch_gr_plan(const GroupArgs& g, const TlItem* sorted, hipStream_t stream);
 // k_gr_render: g.entries and g.keys from `sorted` and the scanned g.klen.
@@ -522,7 +535,7 @@ hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_
 // Numeric field statistics of a finished run (klf_result_field_stats, SPEC.md S4f): per stream and
 // over all streams, how many lines of H carry `key` with a value behind it, and the minimum,
 // maximum, sum and nearest-rank quantiles of those values.
-//   k_fs_count / k_tl_scan    H lines per kMatchChunk chunk, their exclusive prefix -> n = |H|
+//   k_tl_count<false> / k_tl_scan   H lines per kMatchChunk chunk, their exclusive prefix -> n = |H|
 //   k_fs_extract              the selected-line walk over H, one lane per line: the extractor of
 //                             klf_fieldval.hpp over the content, 16 bytes a load; val[rank] /
 //                             cs[rank] = the line's value / segment and class, rank = its place in
@@ -530,11 +543,11 @@ hipError_t launch_gr_render(const GroupArgs& g, const TlItem* sorted, hipStream_
 //                             halves of the 128-bit sum (a wave adds once per run of lines of one
 //                             segment); hits per chunk
 //   k_tl_scan (twice)         the prefix of the chunks' hits -> n_hits; of the segments' hits
-//   k_fs_compact / k_tl_digits   one TlItem per hit, in rank order: key = (segment, value ^ 2^63),
+//   k_fs_compact              one TlItem per hit, in rank order: key = (segment, value ^ 2^63),
 //                             ord = rank
-//   launch_tl_pass            the timeline's stable LSD passes: digits 0..7 order by value (then
-//                             k_fs_rows takes the all-streams row), digits 8..11 by segment (then
-//                             k_fs_rows takes the segments' rows)
+//   the sort (SortArgs)       in two stages: digits 0..7 order by value (then k_fs_rows takes the
+//                             all-streams row), digits 8..11 by segment (then k_fs_rows takes the
+//                             segments' rows)
 // Equal values keep their rank order, so the first item of a run of equal values is its lowest
 // (stream, line).  No kernel waits on another block: kernel boundaries are the only ordering.
 struct FsRow {        // what k_fs_rows leaves per row (the counts and sums are in FieldArgs::tab)
@@ -553,7 +566,7 @@ struct FieldArgs {
   uint32_t n_q;
   uint16_t q[kFsMaxQuantiles];        // permyriad
   uint64_t* cbase;          // [nchunks + 1] H lines per chunk, then their exclusive prefix and n
-  uint64_t n;               // |H| (known after launch_fs_count)
+  uint64_t n;               // |H| (known after launch_tl_count)
   uint64_t* hbase;          // [nchunks + 1] hits per chunk, then their exclusive prefix and n_hits
   uint64_t n_hits;          // (known after launch_fs_extract)
   int64_t* val;             // [n] a hit's value (0 otherwise)
@@ -562,15 +575,12 @@ struct FieldArgs {
                             // sum of v >> 32 (two's complement), sum of v & 0xFFFFFFFF
   uint64_t* hpre;           // [nsegs + 1] the segments' hits, then their exclusive prefix and n_hits
   TlItem* items;            // [n_hits] the sort's input
-  uint64_t* dhist;          // [kTlDigits * 256] (zeroed by launch_fs_compact)
   FsRow* rows;              // [nsegs + 1]: the segments, then all streams
   int64_t* qv;              // [(nsegs + 1) * n_q]
 };
-// k_fs_count + k_tl_scan: g.cbase[g.v.nchunks] = |H| afterwards.
-hipError_t launch_fs_count(const FieldArgs& g, hipStream_t stream, int num_cus);
 // Zeroes g.tab, then k_fs_extract and the two scans: g.hbase[g.v.nchunks] = n_hits afterwards.
 hipError_t launch_fs_extract(const FieldArgs& g, hipStream_t stream, int num_cus);
-// k_fs_compact into g.items, then g.dhist (k_tl_digits).
+// k_fs_compact into g.items.
 hipError_t launch_fs_compact(const FieldArgs& g, hipStream_t stream, int num_cus);
 // k_fs_rows over `sorted` (null with n_hits = 0): all != 0 the all-streams row (items in value
 // order), else the segments' rows (items in (segment, value) order).
@@ -597,8 +607,8 @@ hipError_t launch_pipeline(const RunArgs& a, hipStream_t stream, hipEvent_t* ev,
 hipError_t launch_retail(const RunArgs& a, hipStream_t stream, hipEvent_t* ev, int num_cus,
                          uint32_t* ev_mask = nullptr, const RegroupArgs* g = nullptr,
                          const WindowArgs* tw = nullptr);
-// Zeroes g.table and counts into it (k_hist), between the events ev0 and ev1.
-hipError_t launch_hist(const HistArgs& g, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int num_cus);
+// Zeroes g.table and counts into it (k_hist).
+hipError_t launch_hist(const HistArgs& g, hipStream_t stream, int num_cus);
 // Data statistics (kGramHistWords u32, zeroed here) of the first `sample` bytes of each of
 // up to 16 segments: byte counts, and the 2-grams at even offsets (folded like the
 // prefilter's grams).

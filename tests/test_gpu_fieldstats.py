@@ -254,6 +254,42 @@ def test_chunks_and_rounds(big_session):
     s.check(b"took=", 0, False)
 
 
+# ------------------------------------------- 4a. the sort at its block boundaries ---
+
+SIXTEEN = (0, 1, 100, 500, 1000, 2500, 3333, 5000, 6667, 7500, 9000, 9500, 9900, 9990, 9999, 10000)
+
+
+def _sort_size_streams(n_hits):
+    """n_hits lines with a value over two streams, a few lines without the key or with a bad value
+    between them.  The values: small ones of either sign, every fifth beyond 2^32 (either sign),
+    every fourth the same 42: both stages of the sort move items, and ties exist."""
+    lines = []
+    for i in range(n_hits):
+        v = (i * 7919) % 2003 - 1000
+        if i % 5 == 0:
+            v += (1 + i % 7) * (1 << 32) * (1 if i % 2 else -1)
+        if i % 4 == 3:
+            v = 42
+        lines.append(b"req %d lat=%d done\n" % (i, v))
+        if i % 97 == 50:
+            lines.append(b"no field in this line\n")
+        if i % 101 == 60:
+            lines.append(b"lat=oops\n")
+    lines = [_ts(k) + ln for k, ln in enumerate(lines)]
+    cut = max(1, len(lines) * 2 // 5)
+    return [b"".join(lines[:cut]), b"".join(lines[cut:])]
+
+
+@pytest.mark.parametrize("n_hits", [1, 2047, 2048, 2049, 4097])  # one item; T - 1, T, T + 1, 2 T + 1 for kTlSortBlock
+def test_sort_sizes(gpu, n_hits):
+    with Session(_sort_size_streams(n_hits)) as s:
+        rows, qv = s.check(b"lat=", quantiles=SIXTEEN)
+        assert rows[2]["hits"] == n_hits and len(qv[2]) == 16
+        if n_hits > 1:
+            assert rows[0]["hits"] and rows[1]["hits"] and rows[2]["bad"] and rows[2]["lines"] > n_hits + rows[2]["bad"]
+            assert rows[2]["min"] < -(1 << 32) and rows[2]["max"] > (1 << 32) and 42 in qv[2]
+
+
 # --------------------------------------------------------------- 5. a sum beyond 64 bits ---
 
 def test_sum_beyond_64_bits(gpu):

@@ -3,6 +3,7 @@ against the reference of tests/test_groups_ref.py.  Every call is compared in fu
 all entry records, the key bytes, n_groups and n_lines; with a `top` that holds every group,
 the counts also add up to n_lines and to the result's own counts."""
 import os
+import random
 import subprocess
 
 import pytest
@@ -13,7 +14,7 @@ from klogs_amd import synth
 from test_gpu_regroup import PATTERN_SETS
 from test_gpu_window import SMALL, _based_streams
 from test_groups_ref import (BAD_OPTS, BIG_N, BY_HAND, GroupsRef, big_streams, cli_bodies, grouped, groups_opts,
-                             odd_streams, render_tsv, sixty_four_keys)
+                             odd_streams, render_tsv, sixty_four_keys, _ts)
 
 pytestmark = pytest.mark.gpu
 
@@ -139,6 +140,31 @@ def test_chunks_and_rounds(big_session):
     s.check(10, True)
     s.check(ALL, True, 12)
     s.check(1, False, 30)
+
+
+# ------------------------------------------- 3a. the sort at its block boundaries ---
+
+def _sort_size_streams(n_groups):
+    """n_groups distinct keys whose counts cycle over 2, 1, 3, 1, 1, so that the order is decided
+    partly by count and partly by first line: every group once in a shuffled order, then the
+    further lines of the groups with more than one, shuffled again; cut into two streams."""
+    rng = random.Random(n_groups)
+    first = list(range(n_groups))
+    rng.shuffle(first)
+    more = [g for g in range(n_groups) for _ in range((2, 1, 3, 1, 1)[g % 5] - 1)]
+    rng.shuffle(more)
+    lines = [_ts(i) + b"grp %05d seen\n" % g for i, g in enumerate(first + more)]
+    cut = max(1, len(lines) * 2 // 5)
+    return [b"".join(lines[:cut]), b"".join(lines[cut:])]
+
+
+@pytest.mark.parametrize("n_groups", [1, 2047, 2048, 2049, 4097])  # one item; T - 1, T, T + 1, 2 T + 1 for kTlSortBlock
+def test_sort_sizes(gpu, n_groups):
+    with Session(_sort_size_streams(n_groups)) as s:
+        ent, n, n_lines = s.check(top=ALL, mask=False)
+        assert n == len(ent) == n_groups <= ALL and n_lines == sum(x[0] for x in ent)
+        assert {x[0] for x in ent} == ({2} if n_groups == 1 else {1, 2, 3})
+        assert any(x[1] != x[3] for x in ent)  # a group with lines in both streams
 
 
 # ------------------------------------------------------------------------- 4. collisions ---
