@@ -228,6 +228,56 @@ typedef struct klf_window_opts {
 } klf_window_opts;        /* 48 bytes */
 int klf_window(klf_engine* e, klf_result* prev, const klf_window_opts* o, int64_t tail, klf_result** out);
 
+/* Time context across streams over the latest run (SPEC.md S4g; --around): what every stream
+ * logged around the moments something matched.  With A (the anchors) = the matching lines M of
+ * all streams together, the selection becomes G' = the parsed lines l, of any stream, for which
+ * some a in A has ts(a) - before_ns <= ts(l) <= ts(a) + after_ns: both ends closed, exact
+ * integer arithmetic on (sec, nsec) pairs (a duration is split into d / 1e9 and d % 1e9 with a
+ * carry or borrow; one 64-bit nanosecond count would overflow at the years 0000 and 9999).
+ * before_ns reaches back ahead of an anchor, after_ns behind it; the anchor's own stream is
+ * treated like any other.  M is a subset of G'.  With before_ns = after_ns = 0, G' is the parsed
+ * lines whose instant equals some anchor's, which may include lines outside M, also of other
+ * streams: no setting makes the call klf_retail.  Timestamps need not ascend: every line is
+ * decided on its own; an unparseable line has no instant and is never in G'.  Then G'' = G' cut
+ * by [from, until) exactly as klf_window cuts (open bounds: no cut): context is taken from all
+ * of A first, so an anchor outside the window still lends context to lines inside it.  --since
+ * and the tail rule with `tail` run per stream over G'' as they ran over M.  counts.matched =
+ * |G''| per stream; lines / parsed / since_ok do not change; klf_result_match_bits stays M,
+ * klf_result_group_bits is G'', and the histogram, timeline, grouped counts and field statistics
+ * of the new result work on G''.
+ * The contract is klf_regroup's: prev must be the engine's latest result (KLF_ESTATE) and is
+ * stale afterwards.  The call always starts from M and never compounds: a klf_retail of the new
+ * result re-tails over G''; a klf_regroup, klf_window or klf_around of it starts from M again;
+ * the next klf_run / klf_run_device is untouched.  Read again: M (L/8 bytes), the line meta,
+ * the line index (built now if the run left it out) and the first 32 bytes of every parsed line
+ * in the batch, which must still be resident (klf_run_device: the caller's buffer); the batch
+ * is never scanned again.  All scratch of the call (the anchors' sort buffers, 2 x 16 bytes per
+ * anchor, and 32 bytes per merged interval) is freed before it returns.  A run without an
+ * anchor gives a valid empty selection.
+ * klf_result_timing [4] of the new result is the device time of building G' plus the tail
+ * stage's: two event brackets, summed, because the sort's digit read-back puts a host sync
+ * between them (the first bracket spans the build's three small read-backs: the anchor
+ * count, the sort's digit histograms, the interval count).
+ * KLF_EINVAL (checked first, without touching the device, with a klf_last_error text): a null
+ * argument, tail < -1, non-zero flags or _reserved (also a klf_time's), nsec outside [0, 1e9),
+ * a duration above KLF_AROUND_MAX_NS, an engine without patterns.  KLF_ETOOBIG: 2^32 or more
+ * anchors.  KLF_ENOMEM: the scratch does not fit.  Replaces nothing in the reference.  Out of
+ * scope: follow sessions and shard.run_split, as for klf_regroup; a same-stream-only mode;
+ * inversion or line context combined with it. */
+#define KLF_AROUND_MAX_NS ((1ull << 62) - 1)
+typedef struct klf_around_opts {
+  klf_time from, until;          /* [from, until), as klf_window_opts; open bounds = no cut */
+  uint64_t before_ns, after_ns;  /* each <= KLF_AROUND_MAX_NS */
+  uint32_t flags;                /* 0 */
+  uint32_t _reserved;            /* 0 */
+} klf_around_opts;               /* 56 bytes */
+int klf_around(klf_engine* e, klf_result* prev, const klf_around_opts* o, int64_t tail, klf_result** out);
+/* On a klf_around result: the anchors |A|, the disjoint intervals K they merged into, and the
+ * device time in ms of building G' alone, the first of the two brackets of klf_result_timing [4]
+ * (all 0 on every other result, also on a klf_retail of an around result).  Each pointer may be
+ * NULL. */
+int klf_result_around_info(const klf_result* r, uint64_t* anchors, uint64_t* intervals, double* build_ms);
+
 /* ---- results -------------------------------------------------------------------- */
 /* Selected bytes of one stream (host view, D2H on first access; bytes == NULL: len and
  * counts only, no D2H). */

@@ -268,6 +268,8 @@ struct klf_result {
   bool grouped = false;              // selected over klf_regroup's bitmap (the engine's d_gbits)
   uint64_t total_lines = 0, total_out = 0;
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t ar_anchors = 0, ar_intervals = 0;  // a klf_around result: |A| and the merged intervals K,
+  double ar_build_ms = 0.0;                   // and the device time of building G' (part of ms[4])
   uint32_t ev_mask = 0;              // the timing events the run recorded
   int index_mode = KLF_INDEX_FULL;   // how much of the line index the run itself wrote
   // lazily filled host copies
@@ -1776,7 +1778,8 @@ static int ensure_index(klf_engine* e);
 // klf_retail (o null: over the bitmap the latest result was selected from), klf_regroup
 // (o: over G', built first from the run's match bitmap in d_bits) and klf_window (o and tw:
 // G' only when o asks for context or inversion, then cut by the time window when a bound is
-// closed or the engine has no patterns; always from M).
+// closed or the engine has no patterns; always from M).  klf_around (ar, with tw holding its
+// bounds and no context): G' from the anchors' time intervals (around_build), then the same cut.
 static bool window_closed(const klf_window_opts* tw) {
   return tw->from.sec != KLF_TIME_MIN_SEC || tw->until.sec != KLF_TIME_MAX_SEC;
 }
@@ -1798,8 +1801,13 @@ static klf::SelView sel_view(const klf_result* r) {
   return {sel_bits(r), a.meta, a.line_off, a.bytes, a.segs, a.segout, (uint32_t)r->so.size(), a.cap_lines, nchunks};
 }
 
+// Builds klf_around's G' into e->d_gbits (sized by the caller) from the latest run's M; ms = the
+// build's device time, n / k = the anchors and their merged intervals.
+static int around_build(klf_engine* e, const klf_result* prev, const klf_around_opts* o, double& ms, uint64_t& n,
+                        uint64_t& k);
+
 static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
-                       const char* what, const klf_window_opts* tw = nullptr) {
+                       const char* what, const klf_window_opts* tw = nullptr, const klf_around_opts* ar = nullptr) {
   if (int rc = check_latest(e, prev, what)) return rc;
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
@@ -1814,7 +1822,7 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
   // bitmap mode, over d_gbits, like a regrouped result)
   const bool regroup = o && (!tw || o->before || o->after || o->flags);
   const bool cut = tw && (window_closed(tw) || !prev->has_bits);
-  r->grouped = (o || tw) ? (regroup || cut) : prev->grouped;
+  r->grouped = (o || tw) ? (regroup || cut || ar) : prev->grouped;
   r->total_lines = prev->total_lines;
   r->counted = prev->counted;
   r->pcount_ok = prev->pcount_ok;
@@ -1848,6 +1856,14 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
       g.csum = e->d_gsum.as<uint64_t>();  // (nc >= g.v.nchunks chunks)
       a.bits = g.bits_out;
     }
+    double build_ms = 0.0;
+    if (ar) {  // (before the tail stage's bracket: the sort's digit read-back syncs the host)
+      h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
+      if (h == hipSuccess)
+        if (int rc = around_build(e, prev, ar, build_ms, r->ar_anchors, r->ar_intervals)) { delete r; return rc; }
+      a.bits = e->d_gbits.as<uint32_t>();
+      r->ar_build_ms = build_ms;
+    }
     if (cut) {
       if (h == hipSuccess) h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
       wa.v = sel_view(prev);
@@ -1874,7 +1890,7 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
     if ((rmask & 1u) && (rmask >> 5 & 1u)) {
       float ms = 0.f;
       if ((h = hipEventElapsedTime(&ms, e->ev[0], e->ev[5])) != hipSuccess) { delete r; return hip_err(e, h, "re-tail timing"); }
-      r->ms[4] = ms;
+      r->ms[4] = ms + build_ms;
     }
     if ((rmask >> 9 & 1u) && (rmask >> 10 & 1u)) {
       float ms = 0.f;
@@ -1917,6 +1933,28 @@ extern "C" int klf_window(klf_engine* e, klf_result* prev, const klf_window_opts
     return set_err(e, KLF_EINVAL, "klf_window: context and inversion need a pattern");
   const klf_regroup_opts g{o->before, o->after, o->flags, 0};
   return retail_impl(e, prev, &g, tail, out, "klf_window", o);
+}
+
+extern "C" int klf_around(klf_engine* e, klf_result* prev, const klf_around_opts* o, int64_t tail, klf_result** out) {
+  if (!e || !prev || !o || !out || prev->e != e || tail < -1) return KLF_EINVAL;
+  *out = nullptr;
+  if (o->flags || o->_reserved || o->from._reserved || o->until._reserved)
+    return set_err(e, KLF_EINVAL, "klf_around: unknown flag bits or a non-zero _reserved");
+  if (o->from.nsec < 0 || o->from.nsec >= 1000000000 || o->until.nsec < 0 || o->until.nsec >= 1000000000)
+    return set_err(e, KLF_EINVAL, "klf_around: nsec outside [0, 1e9)");
+  if (o->before_ns > KLF_AROUND_MAX_NS || o->after_ns > KLF_AROUND_MAX_NS)
+    return set_err(e, KLF_EINVAL, "klf_around: a duration above KLF_AROUND_MAX_NS");
+  if (!prev->has_bits) return set_err(e, KLF_EINVAL, "klf_around: the engine has no patterns");
+  const klf_window_opts w{o->from, o->until, 0, 0, 0, 0};
+  return retail_impl(e, prev, nullptr, tail, out, "klf_around", &w, o);
+}
+
+extern "C" int klf_result_around_info(const klf_result* r, uint64_t* anchors, uint64_t* intervals, double* build_ms) {
+  if (!r) return KLF_EINVAL;
+  if (anchors) *anchors = r->ar_anchors;
+  if (intervals) *intervals = r->ar_intervals;
+  if (build_ms) *build_ms = r->ar_build_ms;
+  return KLF_OK;
 }
 
 extern "C" int klf_run(klf_engine* e, const klf_filter* f, klf_result** out) {
@@ -2397,6 +2435,61 @@ struct DeviceSort {
 };
 }  // namespace
 
+// klf_around's selection bitmap (SPEC.md S4g; the kernels: klf_kernels.hpp, ArArgs).
+static int around_build(klf_engine* e, const klf_result* prev, const klf_around_opts* o, double& ms, uint64_t& n,
+                        uint64_t& k) {
+  hipStream_t st = e->stream;
+  CallScratch sc(e, "klf_around", "around");
+  klf::TlArgs t{};
+  t.v = sel_view(prev);
+  t.v.bits_in = e->d_bits.as<uint32_t>();  // M: the anchors, whatever prev was selected from
+  uint32_t* gbits = e->d_gbits.as<uint32_t>();
+  if (int rc = sc.alloc(t.cbase, (t.v.nchunks + 1) * 8, "chunk bases")) return rc;
+  if (int rc = sc.start()) return rc;
+  // 1. anchors per chunk -> n
+  HIPCHK(e, klf::launch_tl_count(t.v, t.cbase, false, st, e->num_cus), "launch k_tl_count");
+  n = k = 0;
+  HIPCHK(e, hipMemcpyAsync(&n, t.cbase + t.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H anchor count");
+  HIPCHK(e, hipStreamSynchronize(st), "sync anchor count");
+  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_around: 2^32 or more anchors");
+  if (!n) {  // no anchor: a valid empty selection
+    HIPCHK(e, hipMemsetAsync(gbits, 0, (size_t)(t.v.cap_lines / 32 + 1) * 4, st), "zero selection bitmap");
+    return sc.finish(ms);
+  }
+  // 2. one item per anchor, 3. sorted by instant
+  t.n = n;
+  DeviceSort sort(sc);
+  if (int rc = sort.prepare(n)) return rc;
+  for (int i = 0; i < 2; ++i) t.items[i] = sort.s.items[i];
+  HIPCHK(e, klf::launch_tl_keys(t, false, st, e->num_cus), "launch k_tl_keys");
+  if (int rc = sort.digits()) return rc;
+  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
+  // 4. the merged intervals, 5. the parsed lines inside one
+  klf::ArArgs g{};
+  g.v = t.v;
+  g.v.bits_in = nullptr;
+  g.sorted = sort.sorted();
+  g.n = n;
+  const uint64_t span = o->before_ns + o->after_ns;  // < 2^63
+  g.before_sec = o->before_ns / 1000000000ull;
+  g.before_nsec = (uint32_t)(o->before_ns % 1000000000ull);
+  g.after_sec = o->after_ns / 1000000000ull;
+  g.after_nsec = (uint32_t)(o->after_ns % 1000000000ull);
+  g.span_sec = span / 1000000000ull;
+  g.span_nsec = (uint32_t)(span % 1000000000ull);
+  g.bits_out = gbits;
+  const size_t nb = (size_t)((n + klf::kArBlock - 1) / klf::kArBlock);
+  if (int rc = sc.alloc(g.bsum, (nb + 1) * 8, "head sums")) return rc;
+  HIPCHK(e, klf::launch_ar_heads(g, st), "launch k_ar_heads");
+  HIPCHK(e, hipMemcpyAsync(&k, g.bsum + nb, 8, hipMemcpyDeviceToHost, st), "D2H interval count");
+  HIPCHK(e, hipStreamSynchronize(st), "sync interval count");
+  if (!k || k > n) return set_err(e, KLF_EHIP, "klf_around: interval count out of range");  // (never: anchor 0 opens one)
+  g.k = k;
+  if (int rc = sc.alloc(g.iv, (size_t)k * sizeof(klf::ArIval), "intervals")) return rc;
+  HIPCHK(e, klf::launch_ar_build(g, st, e->num_cus), "launch k_ar_build");
+  return sc.finish(ms);
+}
+
 // Segment -> stream id.
 static std::vector<uint32_t> seg_streams(const klf_result* r) {
   std::vector<uint32_t> v(r->so.size(), 0u);
@@ -2564,7 +2657,7 @@ extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, kl
   if (int rc = sort.prepare(n)) return rc;
   for (int k = 0; k < 2; ++k) g.items[k] = sort.s.items[k];
   if (int rc = sc.alloc(g.side, n * sizeof(klf::TlSide), "side records")) return rc;
-  HIPCHK(e, klf::launch_tl_keys(g, st, e->num_cus), "launch k_tl_keys");
+  HIPCHK(e, klf::launch_tl_keys(g, true, st, e->num_cus), "launch k_tl_keys");
   if (int rc = sort.digits()) return rc;
   if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
   // 4. rendered lengths -> offsets, entries, bytes

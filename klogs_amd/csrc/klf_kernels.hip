@@ -3384,8 +3384,10 @@ __global__ __launch_bounds__(256) void k_tl_scan(uint64_t* __restrict__ a, uint6
   if (t == 255) a[m] = pre;  // (thread 255's range ends at m)
 }
 
-// The selected-line walk over E.  A line's rank in (stream, line) order is the chunk's base +
-// the lines of the block's earlier waves + its rank k in the wave.
+// The selected-line walk over E (EMITTED: the timeline, with a side record per line) or over the
+// view's own bitmap (klf_around's anchors: the items alone).  A line's rank in (stream, line)
+// order is the chunk's base + the lines of the block's earlier waves + its rank k in the wave.
+template <bool EMITTED>
 __global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
   __shared__ WalkLds ws;
   __shared__ uint32_t s_tot[4];
@@ -3393,7 +3395,7 @@ __global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
   const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
   for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
     const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
-    const uint32_t total = walk_publish(ws, g.v, tl_e_word(g.v, w, L), l0);
+    const uint32_t total = walk_publish(ws, g.v, EMITTED ? tl_e_word(g.v, w, L) : view_word(g.v, w, L), l0);
     if (lane == 0) s_tot[wv] = total;
     __syncthreads();
     uint64_t base = g.cbase[c];
@@ -3406,7 +3408,7 @@ __global__ __launch_bounds__(256) void k_tl_keys(TlArgs g) {
       const uint64_t ord = base + q.k;
       if (ord < g.n) {  // (always: n is the scan's total of the same words)
         g.items[0][ord] = TlItem{(uint64_t)sec ^ (1ull << 63), (uint32_t)nsec, (uint32_t)ord};
-        g.side[ord] = TlSide{q.l, q.s, 0u};
+        if (EMITTED) g.side[ord] = TlSide{q.l, q.s, 0u};
       }
     });
   }
@@ -4107,6 +4109,130 @@ __global__ __launch_bounds__(64) void k_fs_rows(FieldArgs g, const TlItem* __res
       r->min_line = line;
       r->min_seg = seg;
     }
+  }
+}
+
+// ================================ time context across streams (klf_around, SPEC.md S4g) ==
+// G' = the parsed lines of any stream whose instant lies in [ts(a) - before, ts(a) + after] for
+// some anchor a, a line of M of any stream.  The anchors' instants (k_tl_count<false> /
+// k_tl_keys<false> over M) are sorted by the shared sort, then
+//   k_ar_heads / k_tl_scan    anchor i opens an interval iff it is the first or its gap to anchor
+//                             i - 1 exceeds before + after; heads per kArBlock anchors, their
+//                             prefix -> K
+//   k_ar_emit                 one record per interval: the head writes the lower end, the last
+//                             anchor before the next head the upper end
+//   k_ar_build                the selected-line walk over the parsed lines, shaped like k_tw_build:
+//                             a binary search for the last interval whose lower end is <= ts
+// All arithmetic is on (sec, nsec) pairs with a carry or borrow: the years 0000 and 9999 do not
+// fit one 64-bit nanosecond count.  No kernel waits on another block.
+
+// Sorted neighbours prev <= it: the gap between them exceeds the span before + after.
+__device__ __forceinline__ bool ar_head(const ArArgs& g, const TlItem& prev, const TlItem& it) {
+  uint64_t ds = it.sec_key - prev.sec_key;
+  int64_t dn = (int64_t)it.nsec - (int64_t)prev.nsec;
+  if (dn < 0) {  // (then ds >= 1: the items are sorted)
+    dn += 1000000000;
+    ds -= 1;
+  }
+  return ds > g.span_sec || (ds == g.span_sec && (uint32_t)dn > g.span_nsec);
+}
+// Bit k: the thread's k-th anchor i0 + k (< n) opens an interval.
+__device__ __forceinline__ uint32_t ar_head_mask(const ArArgs& g, uint64_t i0) {
+  uint32_t m = 0;
+  if (i0 >= g.n) return m;
+  TlItem prev = g.sorted[i0 ? i0 - 1 : 0];
+  for (uint32_t k = 0; k < kArPer && i0 + k < g.n; ++k) {
+    const TlItem it = g.sorted[i0 + k];
+    if (i0 + k == 0 || ar_head(g, prev, it)) m |= 1u << k;
+    prev = it;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void k_ar_heads(ArArgs g) {
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint32_t cnt = wave_sum((uint32_t)__popc(ar_head_mask(g, (uint64_t)blockIdx.x * kArBlock + (uint64_t)t * kArPer)));
+  if (lane == 0) s_w[wv] = cnt;
+  __syncthreads();
+  if (t == 0) g.bsum[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ __launch_bounds__(256) void k_ar_emit(ArArgs g) {
+  __shared__ uint32_t s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t i0 = (uint64_t)blockIdx.x * kArBlock + (uint64_t)t * kArPer;
+  const uint32_t mask = ar_head_mask(g, i0), cnt = (uint32_t)__popc(mask);
+  const uint32_t incl = wave_incl_scan_add(cnt, lane);
+  if (lane == 63) s_w[wv] = incl;
+  __syncthreads();
+  uint64_t idx = g.bsum[blockIdx.x] + (incl - cnt);  // the heads ahead of anchor i0
+  for (int k = 0; k < wv; ++k) idx += s_w[k];
+  for (uint32_t k = 0; k < kArPer && i0 + k < g.n; ++k) {
+    const uint64_t i = i0 + k;
+    const TlItem it = g.sorted[i];
+    const int64_t sec = (int64_t)(it.sec_key ^ (1ull << 63));
+    if (mask >> k & 1u) ++idx;
+    if (idx == 0 || idx > g.k) continue;  // (never: anchor 0 is a head, K is the scan's total of the same flags)
+    ArIval& iv = g.iv[idx - 1];
+    if (mask >> k & 1u) {
+      int64_t s = sec - (int64_t)g.before_sec;
+      int32_t ns = (int32_t)it.nsec - (int32_t)g.before_nsec;
+      if (ns < 0) {
+        ns += 1000000000;
+        s -= 1;
+      }
+      iv.lo_sec = s;
+      iv.lo_nsec = ns;
+    }
+    const bool last = i + 1 == g.n || (k + 1 < kArPer ? (mask >> (k + 1) & 1u) != 0 : ar_head(g, it, g.sorted[i + 1]));
+    if (last) {
+      int64_t s = sec + (int64_t)g.after_sec;
+      int32_t ns = (int32_t)it.nsec + (int32_t)g.after_nsec;
+      if (ns >= 1000000000) {
+        ns -= 1000000000;
+        s += 1;
+      }
+      iv.hi_sec = s;
+      iv.hi_nsec = ns;
+    }
+  }
+}
+
+// The line at segp + off has an instant inside one of the K >= 1 intervals.  The search keeps
+// [lo, lo + len) inside [0, K): it reads neither index -1 nor K.
+__device__ __forceinline__ bool ar_line_in(const ArArgs& g, const uint8_t* __restrict__ segp, uint64_t off,
+                                           uint64_t seg_len) {
+  int64_t sec;
+  int32_t nsec;
+  if (!g.k || !line_instant(segp, off, seg_len, sec, nsec)) return false;
+  uint64_t lo = 0;
+  for (uint64_t len = g.k; len > 1;) {
+    const uint64_t half = len >> 1;
+    const ArIval& m = g.iv[lo + half];
+    lo = time_before(sec, nsec, m.lo_sec, m.lo_nsec) ? lo : lo + half;
+    len -= half;
+  }
+  const ArIval iv = g.iv[lo];
+  return !time_before(sec, nsec, iv.lo_sec, iv.lo_nsec) && !time_before(iv.hi_sec, iv.hi_nsec, sec, nsec);
+}
+
+__global__ __launch_bounds__(256) void k_ar_build(ArArgs g) {
+  __shared__ WalkLds ws;
+  __shared__ uint32_t s_out[4][64];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  const uint64_t nw = g.v.cap_lines / 32 + 1;  // words of the bitmaps
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t total = walk_publish(ws, g.v, view_word(g.v, w, L), l0);  // (the previous chunk's s_out is read)
+    s_out[wv][lane] = 0u;
+    __syncthreads();
+    walk_rounds(ws, g.v, total, l0, [&](const WalkLine& q) {
+      if (q.live && ar_line_in(g, g.v.bytes + q.sd.base, q.off, q.sd.len)) atomicOr(&s_out[wv][q.j], 1u << q.b);
+    });
+    __syncthreads();
+    if (w < nw) g.bits_out[w] = s_out[wv][lane];
   }
 }
 
@@ -6003,9 +6129,30 @@ hipError_t launch_sort_pass(const SortArgs& s, uint32_t digit, uint32_t from, hi
   return hipGetLastError();
 }
 
-hipError_t launch_tl_keys(const TlArgs& g, hipStream_t st, int num_cus) {
+hipError_t launch_tl_keys(const TlArgs& g, bool emitted, hipStream_t st, int num_cus) {
   if (!g.n || !g.v.nchunks) return hipSuccess;
-  hipLaunchKernelGGL(k_tl_keys, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+  const dim3 grid(chunk_grid(g.v.nchunks, num_cus));
+  if (emitted) hipLaunchKernelGGL(k_tl_keys<true>, grid, dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(k_tl_keys<false>, grid, dim3(256), 0, st, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_ar_heads(const ArArgs& g, hipStream_t st) {
+  const uint64_t nb = (g.n + kArBlock - 1) / kArBlock;
+  if (nb) {
+    hipLaunchKernelGGL(k_ar_heads, dim3((uint32_t)nb), dim3(256), 0, st, g);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tl_scan, dim3(1), dim3(256), 0, st, g.bsum, nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_ar_build(const ArArgs& g, hipStream_t st, int num_cus) {
+  const uint64_t nb = (g.n + kArBlock - 1) / kArBlock;
+  if (!nb || !g.k || !g.v.nchunks) return hipSuccess;
+  hipLaunchKernelGGL(k_ar_emit, dim3((uint32_t)nb), dim3(256), 0, st, g);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ar_build, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
   return hipGetLastError();
 }
 

@@ -475,8 +475,9 @@ struct TlArgs {
   TlEntry* entries;         // [n]
   uint8_t* out;             // the merged bytes
 };
-// k_tl_keys into g.items[0] / g.side.
-hipError_t launch_tl_keys(const TlArgs& g, hipStream_t stream, int num_cus);
+// k_tl_keys into g.items[0] / g.side over E; emitted false: over g.v's own bitmap, the items
+// alone (g.side unread), for klf_around's anchors.
+hipError_t launch_tl_keys(const TlArgs& g, bool emitted, hipStream_t stream, int num_cus);
 // k_tl_plan + k_tl_scan over the sorted g.items[which]: g.psum[blocks] = the merged length.
 hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t stream);
 // k_tl_copy: g.entries and g.out from the sorted g.items[which] and the scanned g.psum.
@@ -585,6 +586,41 @@ hipError_t launch_fs_compact(const FieldArgs& g, hipStream_t stream, int num_cus
 // k_fs_rows over `sorted` (null with n_hits = 0): all != 0 the all-streams row (items in value
 // order), else the segments' rows (items in (segment, value) order).
 hipError_t launch_fs_rows(const FieldArgs& g, const TlItem* sorted, uint32_t all, hipStream_t stream);
+
+// Time context across streams over a finished run (klf_around, SPEC.md S4g): G' = the parsed
+// lines of any stream whose instant lies in [ts(a) - before, ts(a) + after] for some anchor a, a
+// line of M of any stream.
+//   k_tl_count<false> / k_tl_scan   anchors per kMatchChunk chunk of M, their exclusive prefix -> n
+//   k_tl_keys<false>          the selected-line walk over M: one TlItem per anchor, its instant
+//   the sort (SortArgs)       by instant
+//   k_ar_heads / k_tl_scan    interval heads per kArBlock sorted anchors, their prefix -> K
+//   k_ar_emit                 the K disjoint closed intervals, ascending
+//   k_ar_build                the selected-line walk over the parsed lines: a binary search per line
+// No kernel waits on another block: kernel boundaries are the only ordering.
+struct alignas(32) ArIval {  // [lo, hi], both ends closed; the search reads the first 16 bytes
+  int64_t lo_sec;
+  int32_t lo_nsec, hi_nsec;
+  int64_t hi_sec;
+  uint64_t _pad;
+};
+static_assert(sizeof(ArIval) == 32, "interval records");
+constexpr uint32_t kArPer = 8;                  // consecutive sorted anchors per thread
+constexpr uint32_t kArBlock = 256 * kArPer;     // per block of k_ar_heads / k_ar_emit
+struct ArArgs {
+  SelView v;                // bits_in null: k_ar_build walks the parsed lines
+  const TlItem* sorted;     // [n] the anchors by instant
+  uint64_t n;
+  uint64_t before_sec, after_sec, span_sec;     // the durations and their sum as (sec, nsec)
+  uint32_t before_nsec, after_nsec, span_nsec;
+  uint64_t* bsum;           // [ceil(n / kArBlock) + 1] heads per block, then their prefix and K
+  ArIval* iv;               // [k]
+  uint64_t k;               // K (known after launch_ar_heads)
+  uint32_t* bits_out;       // G', the layout of M
+};
+// k_ar_heads + k_tl_scan: g.bsum[blocks] = K afterwards.
+hipError_t launch_ar_heads(const ArArgs& g, hipStream_t stream);
+// k_ar_emit into g.iv, then k_ar_build into g.bits_out (every word of it).  Nothing with K = 0.
+hipError_t launch_ar_build(const ArArgs& g, hipStream_t stream, int num_cus);
 
 // Enqueues the whole pipeline on `stream`; `ev` (6 events) brackets the stages for
 // per-kernel timing: ev[0] start, ev[1] after the workspace memsets, ev[2] after the

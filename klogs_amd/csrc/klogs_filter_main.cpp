@@ -3,6 +3,7 @@
 //
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
 //                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
+//                [--around D] [--around-before D] [--around-after D]
 //                [--merge [--merge-timestamps]] [--top K [--top-mask-digits] [--top-key-bytes N]]
 //                [--stat KEY [--stat-decimals D | --stat-duration]]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
@@ -15,6 +16,13 @@
 // klf_window), before --since and --tail apply: X is an RFC3339Nano instant or a Go duration
 // meaning that long before --now.  They work with and without a pattern and combine with the
 // context flags in one call.
+//
+// --around D keeps every line, of every container, whose timestamp lies within D of a matching
+// line of any container (SPEC.md S4g, klf_around): what the others were doing when it happened.
+// D is a Go duration >= 0 and at most 2^62 - 1 ns; --around-before D / --around-after D set the
+// reach ahead of / behind a match alone and override --around.  They need a --grep or --match,
+// exclude -A / -B / -C / --invert-match, and combine with --from / --until (the cut is made
+// after the context is taken), --since, --tail, --merge, --histogram, --top and --stat.
 //
 // --histogram WIDTH (a Go duration > 0) also writes <logpath>/histogram.tsv: per stream, the
 // lines of the selection (after the pattern, the context flags and the window; before --since
@@ -91,6 +99,10 @@ void usage() {
                "                    context after / before / around a match; the lines that do not match)\n"
                "                    [--from X] [--until X]   (the lines with from <= timestamp < until, before\n"
                "                    --since / --tail apply; X: an RFC3339Nano instant, or a duration before --now)\n"
+               "                    [--around D] [--around-before D] [--around-after D]   (with --grep / --match:\n"
+               "                    the lines of every container within D, a duration >= 0, of a matching line of\n"
+               "                    any container; ahead of / behind a match alone; not with -A / -B / -C /\n"
+               "                    --invert-match)\n"
                "                    [--histogram WIDTH]   (also writes <logpath>/histogram.tsv: the selected lines\n"
                "                    per stream in buckets of WIDTH, a duration > 0, from --from (else the --since\n"
                "                    instant; one of them is needed) up to --until (else --now), at most 65536\n"
@@ -124,6 +136,8 @@ int main(int argc, char** argv) {
   bool regrouped = false;  // any of -A / -B / -C / --invert-match
   std::string from_arg, until_arg;
   bool from_set = false, until_set = false;  // --from / --until
+  std::string around_arg, around_before_arg, around_after_arg;
+  bool around_set = false, around_before_set = false, around_after_set = false;  // --around, -before, -after
   std::string hist_arg;
   bool hist_set = false;  // --histogram
   bool merge = false, merge_ts = false;  // --merge, --merge-timestamps
@@ -163,6 +177,9 @@ int main(int argc, char** argv) {
     else if (a == "--invert-match") { regroup.flags |= KLF_REGROUP_INVERT; regrouped = true; }
     else if (a == "--from") { from_arg = val(); from_set = true; }
     else if (a == "--until") { until_arg = val(); until_set = true; }
+    else if (a == "--around") { around_arg = val(); around_set = true; }
+    else if (a == "--around-before") { around_before_arg = val(); around_before_set = true; }
+    else if (a == "--around-after") { around_after_arg = val(); around_after_set = true; }
     else if (a == "--histogram") { hist_arg = val(); hist_set = true; }
     else if (a == "--merge") merge = true;
     else if (a == "--merge-timestamps") merge_ts = true;
@@ -188,6 +205,8 @@ int main(int argc, char** argv) {
   }
   if (manifest.empty()) usage();
   if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
+  const bool around = around_set || around_before_set || around_after_set;
+  if (around && ((greps.empty() && matches.empty()) || regrouped)) usage();  // around what? / no line context with it
   if (merge_ts && !merge) usage();
   if ((top_set && top.top == 0) || ((top_mask || top_key_set) && !top_set)) usage();
   if (top_mask) top.flags |= KLF_GROUPS_MASK_DIGITS;
@@ -210,6 +229,18 @@ int main(int argc, char** argv) {
   if (from_set) bound(from_arg, &window.from);
   if (until_set) bound(until_arg, &window.until);
   const bool windowed = from_set || until_set;
+  // --around: both reaches, then each one's own flag; the bounds ride along
+  klf_around_opts around_opts{window.from, window.until, 0, 0, 0, 0};
+  auto reach = [&](const std::string& v) -> uint64_t {
+    int64_t ns = 0;
+    char perr[256];
+    if (klh_parse_duration(v.c_str(), &ns, perr, sizeof(perr)) != KLH_OK || ns < 0 || (uint64_t)ns > KLF_AROUND_MAX_NS)
+      usage();
+    return (uint64_t)ns;
+  };
+  if (around_set) around_opts.before_ns = around_opts.after_ns = reach(around_arg);
+  if (around_before_set) around_opts.before_ns = reach(around_before_arg);
+  if (around_after_set) around_opts.after_ns = reach(around_after_arg);
   if (logpath.empty()) {  // defaultLogPath (:47)
     char buf[128];
     klh_default_log_path(now.sec, buf, sizeof(buf));
@@ -330,10 +361,16 @@ int main(int argc, char** argv) {
     // context / inversion: the run itself with --tail 0 (the cheapest run that leaves the
     // line index and the match bitmap behind), then klf_regroup applies the user's tail
     const int64_t user_tail = filter.tail;
-    if (regrouped || windowed) filter.tail = 0;
+    if (regrouped || windowed || around) filter.tail = 0;
     rc = klf_run(e, &filter, &r);
     if (rc != KLF_OK) panic_exit(std::string("klf_run: ") + klf_strerror(rc) + ": " + klf_last_error(e));
-    if (windowed) {  // (with the context flags, if any, in the one call)
+    if (around) {  // (with the window, if any, in the one call)
+      klf_result* g = nullptr;
+      rc = klf_around(e, r, &around_opts, user_tail, &g);
+      if (rc != KLF_OK) panic_exit(std::string("klf_around: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      klf_result_free(r);
+      r = g;
+    } else if (windowed) {  // (with the context flags, if any, in the one call)
       klf_result* g = nullptr;
       rc = klf_window(e, r, &window, user_tail, &g);
       if (rc != KLF_OK) panic_exit(std::string("klf_window: ") + klf_strerror(rc) + ": " + klf_last_error(e));

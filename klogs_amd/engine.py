@@ -30,6 +30,7 @@ KLF_PAT_REGEX = 1
 GO_ZERO_TIME = (-62135596800, 0)
 TIME_MIN_SEC = -(1 << 63)     # KLF_TIME_MIN_SEC: klf_window_opts.from.sec, open below
 TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, open above
+AROUND_MAX_NS = (1 << 62) - 1  # KLF_AROUND_MAX_NS: klf_around_opts.before_ns / after_ns at most
 HIST_MAX_BUCKETS = 65536      # KLF_HIST_MAX_BUCKETS: klf_hist_opts.n_buckets at most
 TIMELINE_TIMESTAMPS = 1       # KLF_TIMELINE_TIMESTAMPS: render each line's prefix too
 TIMELINE_MAX_TAG = 1024       # KLF_TIMELINE_MAX_TAG: bytes of one stream's tag at most
@@ -73,6 +74,11 @@ class _RegroupOpts(C.Structure):
 
 class _WindowOpts(C.Structure):
     _fields_ = [("from_", _Time), ("until", _Time), ("before", C.c_uint32), ("after", C.c_uint32),
+                ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class _AroundOpts(C.Structure):  # klf_around_opts (56 bytes)
+    _fields_ = [("from_", _Time), ("until", _Time), ("before_ns", C.c_uint64), ("after_ns", C.c_uint64),
                 ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
@@ -144,6 +150,9 @@ SIGNATURES = {
     "klf_retail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_regroup": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_RegroupOpts), C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_window": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_WindowOpts), C.c_int64, C.POINTER(C.c_void_p)]),
+    "klf_around": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_AroundOpts), C.c_int64, C.POINTER(C.c_void_p)]),
+    "klf_result_around_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_double)]),
     "klf_result_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                     C.POINTER(_Counts)]),
     "klf_result_lines": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -751,6 +760,35 @@ class Result:
         r = C.c_void_p()
         _check(_lib.klf_window(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
         return Result(r.value or 0, self.n_streams, self._eng)
+
+    def around(self, before_ns: int = 0, after_ns: int = 0, from_: Optional[Tuple[int, int]] = None,
+               until: Optional[Tuple[int, int]] = None, tail: int = -1, flags: int = 0) -> "Result":
+        """The same run with time context across streams (klf_around, SPEC.md S4g): every parsed
+        line, of every stream, whose instant lies in [ts(a) - before_ns, ts(a) + after_ns] of a
+        matching line a of any stream, then cut to [from_, until) as `window` cuts, then --since
+        and --tail N.  Always from the run's own matches.  This result is stale afterwards."""
+        o = _AroundOpts()
+        lo = (TIME_MIN_SEC, 0) if from_ is None else from_
+        hi = (TIME_MAX_SEC, 0) if until is None else until
+        o.from_.sec, o.from_.nsec = int(lo[0]), int(lo[1])
+        o.until.sec, o.until.nsec = int(hi[0]), int(hi[1])
+        o.before_ns, o.after_ns = int(before_ns), int(after_ns)
+        o.flags = int(flags)
+        r = C.c_void_p()
+        _check(_lib.klf_around(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
+        return Result(r.value or 0, self.n_streams, self._eng)
+
+    def around_counts(self) -> Tuple[int, int]:
+        """klf_result_around_info: (anchors, merged intervals) of an `around` result."""
+        n, k = C.c_uint64(), C.c_uint64()
+        _check(_lib.klf_result_around_info(self._p, C.byref(n), C.byref(k), None))
+        return int(n.value), int(k.value)
+
+    def around_build_ms(self) -> float:
+        """klf_result_around_info: the device time of building the selection alone (part of timing()[4])."""
+        ms = C.c_double()
+        _check(_lib.klf_result_around_info(self._p, None, None, C.byref(ms)))
+        return float(ms.value)
 
     def free(self):
         if self._p:
