@@ -20,17 +20,18 @@ int klf_debug_match(const klf_pattern* pats, uint32_t n, const uint8_t* content,
 /* The prefiltered path of general sets on one content, as the scan runs it: q-gram
  * samples at positions = phase (mod stride), bitmap + bucket verification, literal hits
  * final, regex factor hits -> Glushkov NFA; anchored short needles at every position
- * holding the anchor byte.  info (nullable, 5 words) = {prefilter on, q, stride, needles,
- * 0x100 | anchor byte (0: no anchor)}; when the prefilter is off *match is the full
- * matcher's answer. */
+ * holding the anchor byte.  info (nullable, 7 words) = {prefilter on, q, stride, needles,
+ * 0x100 | anchor byte (0: no anchor), K, the exact probe's multiplier (0: another kind)};
+ * when the prefilter is off *match is the full matcher's answer. */
 int klf_debug_prefilter(const klf_pattern* pats, uint32_t n, const uint8_t* content, size_t len,
                         uint32_t phase, int* match, uint32_t* info);
 
 /* The prefilter's layout chosen on the statistics of `sample` (the host twin of the first
  * batch's k_gramhist; slen 0: the compile-time layout), then its work over `data`:
- * out[9] = {stride, q, K, 0x100 | anchor byte (0: none), probes, bitmap hits, anchor hits,
- * verified needle occurrences, samples past the two-level probe's 2-gram stage}; layout
- * (cap bytes) gets the layout's description. */
+ * out[11] = {stride, q, K, 0x100 | anchor byte (0: none), probes, bitmap hits, anchor hits,
+ * verified needle occurrences, samples past the two-level probe's 2-gram stage, distinct
+ * probed grams, the exact probe's multiplier (0: another kind)}; layout (cap bytes) gets the
+ * layout's description. */
 int klf_debug_prefilter_hits(const klf_pattern* pats, uint32_t n, const uint8_t* sample, size_t slen,
                              const uint8_t* data, size_t dlen, uint64_t* out, char* layout, size_t cap);
 

@@ -1446,6 +1446,7 @@ static void fill_args(const RunPlan& p, const RunState& s, int attempt, klf::Run
   a.lit = e->d_lit.as<uint8_t>(); a.lit_words = e->d_lit.as<uint32_t>(); a.lit_len = (uint32_t)e->cs.literal.size();
   a.lit_anchor = e->cs.literal_anchor;
   a.lit_anchor_byte = e->cs.literal.empty() ? 0u : e->cs.literal[e->cs.literal_anchor];
+  a.qf_mul = e->cs.qf_mul;
   memcpy(static_cast<void*>(&a.pats), &e->dpats, sizeof(a.pats));
   // the workspace
   a.tstat = e->d_tstat.as<klf::TileStat>(); a.tile_base = e->d_tile_base.as<uint64_t>(); a.bsum = e->d_bsum.as<uint64_t>();
@@ -3329,6 +3330,8 @@ extern "C" int klf_debug_prefilter(const klf_pattern* pats, uint32_t n, const ui
     info[2] = cs.qf_stride;
     info[3] = cs.qf_needles;
     info[4] = cs.qf_anc_on ? 0x100u | cs.qf_anc_byte : 0u;
+    info[5] = cs.qf_k;
+    info[6] = cs.qf_mul;
   }
   if (cs.mode != klf::CompiledSet::kGeneral || !cs.qf_on) return klf_debug_match(pats, n, content, len, match);
   // also_all: the engine's filter is kAll's (every parsed line); the other patterns' tables
@@ -3366,6 +3369,8 @@ extern "C" int klf_debug_prefilter_hits(const klf_pattern* pats, uint32_t n, con
   out[6] = h.anchor_hits;
   out[7] = h.verified;
   out[8] = h.pair_pass;
+  out[9] = cs.qf_grams;
+  out[10] = cs.qf_mul;
   if (layout && cap) { strncpy(layout, cs.qf_layout.c_str(), cap - 1); layout[cap - 1] = 0; }
   return KLF_OK;
 }

@@ -1010,11 +1010,14 @@ struct QProbe {
   static constexpr bool kMidIdx = QQ == 3 && QK == 2;  // word from h bits 18..29 (qf_bucket)
   static constexpr bool K3 = QK == 3 || QK == (int)kQfTwoLevel;  // three bits per gram
   static constexpr bool TWO = QK == (int)kQfTwoLevel;            // pair stage first (stride 4 only)
+  static constexpr bool EX = QK == (int)kQfExact;                // the table holds the grams (stride 4 only)
   static_assert(!TWO || QS == 4, "the two-level probe runs at stride 4");
+  static_assert(!EX || QS == 4, "the exact probe runs at stride 4");
   static_assert(QQ == 3 || QQ == 4, "3- or 4-byte grams");
   const uint32_t* s_qf;   // the needles' q-gram bitmap (LDS)
   const uint8_t* s_tile;  // the staged tile (LDS)
-  uint32_t fold;
+  uint32_t fold;          // (exact probe, 3-byte grams: | 0xFF000000, qf_exact_word)
+  uint32_t mul;           // exact probe: the set's multiplier (qf_exact_slot), else unused
   // bit 0 of test(): gram g has all K bits of its bitmap word set (qf_f / qf_hash /
   // qf_bits): the multiplies, the word read, and the bit positions as byte / word selects
   // or low bits of the products (SDWA operands of the shifts)
@@ -1044,9 +1047,21 @@ struct QProbe {
     if (TWO) t &= shr_byte1(w, r.m);  // the fourth bit: m bits 8..12 (qf_bits)
     return t;
   }
+  // Exact probe (qf_exact_slot / qf_exact_word): the sample as the table holds a gram, and
+  // its slot's word -- bits 18..29 of the 24-bit product as the LDS byte offset, one SDWA AND
+  __device__ __forceinline__ uint32_t ex_sample(uint32_t g) const { return g | fold; }
+  __device__ __forceinline__ uint32_t ex_word(uint32_t gf) const {
+    const uint32_t a = (mul_u24(gf, mul) >> 16) & ((kQfWords - 1u) << 2);
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_qf) + a);
+  }
   __device__ __forceinline__ uint32_t hbits(uint32_t g) const {
-    const Hash r = hash(g);
-    return test(word(r), r);
+    if constexpr (EX) {
+      const uint32_t gf = ex_sample(g);
+      return ex_word(gf) == gf ? 1u : 0u;
+    } else {
+      const Hash r = hash(g);
+      return test(word(r), r);
+    }
   }
   // the samples of chunk ch (16 B) -> their grams, in order (QS = 8: dwords 0 and 2;
   // QS = 6: the grid's bytes 0, 6 and 12, qf_sampled)
@@ -1169,6 +1184,28 @@ struct QProbe {
     }
     return chit;
   }
+  // the exact probe's fast pass: the lanes with a hit, as a wave-uniform mask (each compare's
+  // lane mask OR-ed on the scalar unit: no per-lane accumulator, no positions).  Same shape
+  // as fast_pairs: two chunks per step, their eight table reads in flight before the first
+  // compare.  Samples past the tile's end may count here; positions() clips them.
+  __device__ __forceinline__ uint64_t fast_exact(const ScanTile& c) const {
+    const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
+    uint64_t lanes = 0;
+#pragma unroll
+    for (int v = 0; v < (ABL(c, 4) ? 0 : 8); v += 2) {
+      const uint4 xa = lane_chunk(s_tile, c, ((uint32_t)v + rot) & 7u);
+      const uint4 xb = lane_chunk(s_tile, c, ((uint32_t)v + 1u + rot) & 7u);
+      const uint32_t g[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+      uint32_t gf[8], w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gf[k] = ex_sample(g[k]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[k] = ex_word(gf[k]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) lanes |= __ballot(w[k] == gf[k]);
+    }
+    return lanes;
+  }
   __device__ __forceinline__ uint32_t fast_chunks(const ScanTile& c) const {  // every other stride
     const uint32_t rot = ((uint32_t)c.lane >> 1) & 7u;
     uint32_t chit = 0;
@@ -1195,6 +1232,9 @@ struct QProbe {
                                       uint32_t& xh) const {
     if constexpr (TWO) {
       two_level(c, s_list, nlines, hq, xh);
+    } else if constexpr (EX) {
+      const uint64_t lanes = fast_exact(c);
+      if (lanes) positions(c, ((lanes >> c.lane) & 1u) ? 0xFFu : 0u, hq);  // a hit lane probes its chunks again
     } else {
       const uint32_t chit = (QS == 4 || QS == 6) ? fast_pairs(c) : fast_chunks(c);
       if (__any(chit != 0)) positions(c, chit, hq);
@@ -1463,7 +1503,9 @@ __global__ __launch_bounds__(kThreads, MODE == kScanGen ? 3 : KLF_SCAN_OCC) void
     uint32_t tile_hits = 0;
     if constexpr (GEN) {
       uint32_t hq[4] = {0u, 0u, 0u, 0u}, xh = kNoHit;
-      const QProbe<QS, QK, QQ> probe{s_qf, s_tile, a.pats.qf_fold};
+      constexpr bool EX = QK == (int)kQfExact;
+      const QProbe<QS, QK, QQ> probe{s_qf, s_tile, a.pats.qf_fold | ((EX && QQ == 3) ? 0xFF000000u : 0u),
+                                     EX ? a.qf_mul : 0u};
       probe.run(c, s_list, tl.nlines, hq, xh);
       if (ANC && __any(any.anc != 0)) anchored_hits(a.pats, s_tile, c, any.anc, pat, afold, hq);
       if (ABL(c, 8)) {  // timing build: probes only
@@ -2259,7 +2301,7 @@ __device__ void verify_hit(const RunArgs& a, uint32_t tile, uint32_t s, int32_t 
   const int64_t rel_lo = (int64_t)(tile - sd.tile0) * kTile;
   const uint32_t gs = gword(a.bytes + sd.base + rel_lo + p);
   const uint32_t g = (gs | P.qf_fold) & P.qf_mask;
-  const uint32_t b = qf_bucket(g, P.qf_w24, P.qf_k);
+  const uint32_t b = qf_bucket(g, P.qf_w24, P.qf_k, a.qf_mul);
   verify_hit_from(a, tile, s, sd, p, gs, P.qf_head[b], P.qf_head[b + 1], vq);
 }
 
@@ -2307,7 +2349,7 @@ __device__ __forceinline__ void verify_body(RunArgs& a, uint32_t bid, uint32_t n
     }
 #pragma unroll
     for (int u = 0; u < kVerifyBatch; ++u) {
-      const uint32_t b = qf_bucket((gg[u] | P.qf_fold) & P.qf_mask, P.qf_w24, P.qf_k);
+      const uint32_t b = qf_bucket((gg[u] | P.qf_fold) & P.qf_mask, P.qf_w24, P.qf_k, a.qf_mul);
       e0[u] = P.qf_head[b];
       e1[u] = P.qf_head[b + 1];
     }
@@ -5797,9 +5839,13 @@ hipError_t launch_scan(const RunArgs& a, hipStream_t st, int num_cus) {
 }
 template <int QS, int QQ>
 hipError_t launch_gen_q(const RunArgs& a, hipStream_t st, int num_cus) {
-  if constexpr (QS == 4)
+  if constexpr (QS == 4) {
     if (a.pats.qf_k == kQfTwoLevel)  // the two-level probe (stride 4, no anchor)
       return launch_scan<kScanGen, 4, (int)kQfTwoLevel, QQ>(a, st, num_cus);
+    if (a.pats.qf_k == kQfExact && !a.pats.qf_anc_on)  // the exact probe (stride 4, no anchor)
+      return launch_scan<kScanGen, 4, (int)kQfExact, QQ>(a, st, num_cus);
+  }
+  if (a.pats.qf_k == kQfExact) return hipErrorInvalidValue;  // (another stride, or anchored: no such scan)
   // short needles anchored: only beside stride-8 probes (choose_layout anchors at the long
   // needles' stride, and those are 10 bytes or longer), so no other stride has the variant
   if constexpr (QS == 8)

@@ -100,6 +100,26 @@ constexpr uint32_t kQfPairWords = 2048;
 // them (all 32 banks) for one more VALU per sample measured slower, C4 k_scan 7.60 -> 7.97 ms
 // (same box, two rounds; the variant is in the history): the pair stage is bound by its
 // instructions, not by the conflicts.
+// Exact layout (qf_k = kQfExact, small sets at stride 4, unanchored): the table's 4,096 words
+// hold the probed grams themselves, one per slot and collision-free, so the probe is "my
+// slot's word equals my sample" -- the fold OR, one multiply, the offset AND, the read and a
+// compare, against the Bloom probe's two shifts and and-or more -- and it is exact: only real
+// occurrences of a probed gram reach k_verify.  The slot of a gram is bits 18..29 of its low
+// three bytes times a per-set odd 24-bit multiplier (RunArgs::qf_mul, found by place_tables so
+// that no two grams share a slot); it is the verification bucket too.  A 4-byte gram's slot
+// also comes from its low three bytes; the compare covers all four.  3-byte grams: the table
+// word and the sample both carry 0xFF in the top byte (the sample's is set by the fold OR;
+// the 24-bit multiply ignores it), so the compare is a plain dword compare as well.  An unused
+// slot holds a value whose own slot is another one: no sample that maps there can equal it.
+constexpr uint32_t kQfExact = 6;
+constexpr uint32_t kQfExactMaxGrams = 192;  // distinct grams: exp(-192^2 / (2 * 4096)) = 1.1 % of the multipliers
+                                            // place them all (birthday bound), ~6 of the tries below
+constexpr uint32_t kQfExactTries = 512;     // multipliers tried before the candidate is given up
+__host__ __device__ inline uint32_t qf_exact_slot(uint32_t g, uint32_t mul) {
+  return (((g & 0xFFFFFFu) * mul) >> 18) & (kQfWords - 1u);
+}
+// the table word of a probed gram / what the scan compares of a (folded, masked) sample
+__host__ __device__ inline uint32_t qf_exact_word(uint32_t g, uint32_t w24) { return w24 ? g : g | 0xFF000000u; }
 __host__ __device__ inline uint32_t qf_pair_word(uint32_t p) { return (p >> 5) & (kQfPairWords - 1u); }
 __host__ __device__ inline bool qf_k3(uint32_t k) { return k == 3 || k == kQfTwoLevel; }
 __host__ __device__ inline uint32_t qf_f(uint32_t g, uint32_t k) {
@@ -116,7 +136,8 @@ __host__ __device__ inline uint32_t qf_word(uint32_t h) { return h >> (32 - kQfB
 // (h >> 16) & 0x3FFC is one SDWA AND -- a VALU fewer per probe; the C5 set's bitmap hits
 // on C5 data are unchanged (96 per 32 MiB either way).  (Bits 34..45 of a second product,
 // v_mul_hi_u32_u24: 54x the hits -- a product's top bits follow the gram's top byte.)
-__host__ __device__ inline uint32_t qf_bucket(uint32_t g, uint32_t w24, uint32_t k) {
+__host__ __device__ inline uint32_t qf_bucket(uint32_t g, uint32_t w24, uint32_t k, uint32_t mul = 0u) {
+  if (k == kQfExact) return qf_exact_slot(g, mul);
   if (w24 == 0 && k == 2) return (qf_hash(g, w24, k) >> 18) & (kQfWords - 1u);
   if (k == kQfTwoLevel) return qf_hash(g, w24, k) >> 21;  // [0, kQfPairWords)
   return qf_word(qf_hash(g, w24, k));
@@ -135,7 +156,8 @@ __host__ __device__ inline uint32_t qf_bits(uint32_t g, uint32_t h, uint32_t k) 
 }
 // The whole probe of a (folded, masked) gram against the bitmap (host emulation; the scan
 // computes the same from its LDS copy)
-__host__ __device__ inline bool qf_pass(const uint32_t* bm, uint32_t gq, uint32_t w24, uint32_t k) {
+__host__ __device__ inline bool qf_pass(const uint32_t* bm, uint32_t gq, uint32_t w24, uint32_t k, uint32_t mul = 0u) {
+  if (k == kQfExact) return bm[qf_exact_slot(gq, mul)] == qf_exact_word(gq, w24);
   if (k == kQfTwoLevel && !((bm[qf_pair_word(gq & 0xFFFFu)] >> (gq & 31u)) & 1u)) return false;
   const uint32_t h = qf_hash(gq, w24, k), bits = qf_bits(gq, h, k);
   return (bm[qf_bloom_word(gq, w24, k)] & bits) == bits;
@@ -237,7 +259,7 @@ struct DevPatterns {  // device copies of CompiledSet tables (kGrepGeneral)
   uint32_t rx_unbounded = 0;          // regexes without a bound (k_nfa runs their whole lines)
   // q-gram prefilter (qf_on): bitmap, buckets, needles
   uint32_t qf_on = 0, qf_stride = 1, qf_fold = 0, qf_mask = ~0u;
-  uint32_t qf_w24 = 24, qf_k = 3;     // probe: 4-byte grams (24) or 3-byte (0); bits per gram
+  uint32_t qf_w24 = 24, qf_k = 3;     // probe: 4-byte grams (24) or 3-byte (0); bits per gram (5 two-level, 6 exact)
   const uint32_t* qf_bitmap = nullptr;
   const uint32_t* qf_head = nullptr;
   const uint4* qf_ent = nullptr;
@@ -270,6 +292,9 @@ struct RunArgs {
   uint32_t lit_len;
   uint32_t lit_anchor; // index of the literal's rarest byte (scan anchor)
   uint32_t lit_anchor_byte;  // that byte
+  // the exact probe's multiplier (pats.qf_k == kQfExact; qf_exact_slot).  It belongs with
+  // pats.qf_*; it sits in what was padding here so that no kernel's argument offsets move
+  uint32_t qf_mul;
   const uint32_t* lit_words;  // the literal as little-endian dwords (zero padded)
   DevPatterns pats;
   // workspace (device)

@@ -1493,8 +1493,11 @@ double layout_cost(const CompiledSet& c, const DataStats& st) {
   // gram with two bits (fold, multiply, word offset, two shifts, and / or), 9.9 with the
   // fourth byte, 13.4 for 3 bits (folded gram, two more multiplies, a shift)
   // (two-level: ~5 per sample for the pair stage, the 3-bit probe on the ~5 % survivors)
-  const double per_probe = c.qf_k == kQfTwoLevel ? 6.0 + (c.qf_q == 4 ? 1.0 : 0.0)
-                                                 : 7.0 + (c.qf_q == 4 ? 3.0 : 0.0) + (c.qf_k == 3 ? 6.5 : 0.0);
+  // (exact: 4.0 for either gram length -- fold, multiply, word offset, compare; the lane masks
+  // are OR-ed on the scalar unit -- and no false hits: `hits` below is all of its hits)
+  const double per_probe = c.qf_k == kQfExact      ? 4.0
+                           : c.qf_k == kQfTwoLevel ? 6.0 + (c.qf_q == 4 ? 1.0 : 0.0)
+                                                   : 7.0 + (c.qf_q == 4 ? 3.0 : 0.0) + (c.qf_k == 3 ? 6.5 : 0.0);
   double cost = per_probe * samples / 64.0;
   if (c.qf_anc_on) {
     cost += 60.0;
@@ -1507,7 +1510,14 @@ double layout_cost(const CompiledSet& c, const DataStats& st) {
   return cost + 40.0 * hits;
 }
 
-void place_tables(CompiledSet& out, const DataStats* st);
+bool place_tables(CompiledSet& out, const DataStats* st, bool exact = false);
+
+// KLF_QF_EXACT: 0 never offers the exact probe (kQfExact), force takes it wherever it can be
+// placed (tests / A-B runs; read per call)
+int exact_knob() {
+  const char* v = getenv("KLF_QF_EXACT");
+  return !v ? 1 : !strcmp(v, "0") ? 0 : !strcmp(v, "force") ? 2 : 1;
+}
 
 }  // namespace
 
@@ -1535,11 +1545,20 @@ void place_needles(CompiledSet& out, const DataStats* st) {
   CompiledSet best;
   double best_cost = 0;
   bool have = false;
+  // The exact probe (kQfExact) is one more candidate of every unanchored stride-4 layout, on
+  // the tuned path only (KLF_QF_EXACT=force: wherever it can be placed, and it then wins over
+  // every other kind); a set whose grams find no collision-free table does not get it.
+  // (KLF_QF_TWO=force pins the two-level kind: the exact one then needs its own force)
+  const char* two = getenv("KLF_QF_TWO");
+  const int xknob = (two && !strcmp(two, "force") && exact_knob() == 1) ? 0 : exact_knob();
+  const bool tuned = st && st->nbytes;
   std::vector<std::string> seen;  // layouts already placed (a 3-byte cap can give the 4-byte one's)
   for (uint32_t v = 0; v < variants.size(); ++v)
-    for (int cand = 0; cand < 4; ++cand) {
+    for (int cand = 0; cand < 8; ++cand) {
       const int anchored = cand & 1;
-      const uint32_t qmax = cand < 2 ? 4u : 3u;  // 3-byte grams: a cheaper probe, more hits
+      const bool exact = cand >= 4;
+      if (exact && (anchored || xknob == 0 || !(tuned || xknob == 2))) continue;
+      const uint32_t qmax = (cand & 2) ? 3u : 4u;  // 3-byte grams: a cheaper probe, more hits
       if (qmax == 3 && !(st && st->nbytes)) continue;  // (only the data can say whether they pay)
       if (const char* qv = getenv("KLF_QF_QMAX"))  // ablation: one gram length at the data's layout
         if (st && st->nbytes && (uint32_t)atoi(qv) != qmax) continue;
@@ -1553,23 +1572,35 @@ void place_needles(CompiledSet& out, const DataStats* st) {
       c.rx_pre = ns.rx_pre;
       choose_layout(c, st, anchored != 0, qmax);
       if (anchored && !c.qf_anc_on) continue;  // nothing to anchor: same as the probed layout
+      if (exact && (c.qf_stride != 4 || c.qf_anc_on)) continue;  // (the exact scan: stride 4, unanchored)
       {
-        const std::string key = std::to_string(v) + "/" + c.qf_layout;
+        const std::string key = std::to_string(v) + "/" + c.qf_layout + (exact ? "/exact" : "");
         if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;  // placed already
         seen.push_back(key);
       }
       const auto t0 = std::chrono::steady_clock::now();
-      place_tables(c, st);
+      const bool placed = place_tables(c, st, exact);
       const auto t1 = std::chrono::steady_clock::now();
+      if (!placed) {  // (too many grams, or no multiplier separates them)
+        if (getenv("KLF_DIAG"))
+          fprintf(stderr, "[klf] layout candidate (variant %u): %s k=%u: %u grams not placed (%.0f us)\n", v,
+                  c.qf_layout.c_str(), kQfExact, c.qf_grams, std::chrono::duration<double, std::micro>(t1 - t0).count());
+        continue;
+      }
       double cost;
       if (st && st->nbytes) {
         cost = layout_cost(c, *st);
       } else {  // no statistics: stride first (8 is ~2x cheaper than 4), then the anchor's share
         cost = 1e6 * qf_samples_per_tile(c.qf_stride) / 8192.0 + (c.qf_anc_on ? c.qf_anc_share * 1e3 : 0.0);
       }
-      char buf[64];
-      snprintf(buf, sizeof buf, " k=%u [est %.0f VALU/tile]", c.qf_k, cost);  // (k: bits per gram, 5 = two-level)
+      char buf[96];
+      // (k: bits per gram, 5 = two-level, 6 = exact with its multiplier)
+      if (exact)
+        snprintf(buf, sizeof buf, " k=%u [est %.0f VALU/tile] mul=0x%06x grams=%u", c.qf_k, cost, c.qf_mul, c.qf_grams);
+      else
+        snprintf(buf, sizeof buf, " k=%u [est %.0f VALU/tile]", c.qf_k, cost);
       c.qf_layout += buf;
+      if (exact && xknob == 2) cost -= 1e12;  // forced: ahead of every other kind, the cheapest exact one
       if (getenv("KLF_DIAG"))
         fprintf(stderr, "[klf] layout candidate (variant %u): %s (tables %.0f us, cost %.0f us)\n", v, c.qf_layout.c_str(),
                 std::chrono::duration<double, std::micro>(t1 - t0).count(),
@@ -1599,7 +1630,10 @@ namespace {
 // byte-class estimate -- with a small penalty for grams other needles already sample
 // (bucket length).  Every probed gram sets K bits of one bitmap word (blocked Bloom); an
 // anchored needle has one bucket entry, at its anchor's gram, and no bitmap bits.
-void place_tables(CompiledSet& out, const DataStats* st) {
+// exact (stride 4, unanchored): the table holds the probed grams themselves (kQfExact); false
+// when they are too many or no multiplier of the fixed sequence gives each a slot of its own
+// (out's tables are then unusable and the candidate is dropped).
+bool place_tables(CompiledSet& out, const DataStats* st, bool exact) {
   const uint32_t q = out.qf_q, S = out.qf_stride;
   const bool hist = st && st->pair.size() >= 65536 && st->pair_tot > 0;  // data statistics
   const double nsample = st && st->nbytes ? (double)st->nbytes : 1.0;
@@ -1663,8 +1697,13 @@ void place_tables(CompiledSet& out, const DataStats* st) {
   // probe (an exact 2-gram stage, then three bits; KLF_QF_TWO=0 keeps the one-level one)
   const char* two = getenv("KLF_QF_TWO");
   const bool two_ok = S == 4 && !out.qf_anc_on && !(two && !strcmp(two, "0"));
-  out.qf_k = (two_ok && two && !strcmp(two, "force")) ? kQfTwoLevel
+  out.qf_k = exact ? kQfExact
+             : (two_ok && two && !strcmp(two, "force")) ? kQfTwoLevel
              : nprobed * S <= kQfK2MaxGrams ? 2u : two_ok ? kQfTwoLevel : 3u;
+  out.qf_mul = 0;
+  out.qf_grams = 0;
+  if (exact && (S != 4 || out.qf_anc_on)) return false;
+  std::vector<uint32_t> egram;  // exact: the gram of each entry of bent (its slot follows the multiplier)
   const uint32_t w24 = q == 4 ? 24u : 0u;
   for (uint32_t i = 0; i < n; ++i) {
     const std::string& s = out.qf_needle[i];
@@ -1701,6 +1740,11 @@ void place_tables(CompiledSet& out, const DataStats* st) {
     for (uint32_t j = 0; j < S; ++j) {
       const uint32_t k = best_a + j, g = gram_at(s, k);
       used.add(g);
+      if (exact) {
+        egram.push_back(g);
+        bent.push_back({0u, i << 8 | k});
+        continue;
+      }
       const uint32_t h = qf_hash(g, w24, out.qf_k);
       const uint32_t bw = qf_bucket(g, w24, out.qf_k);
       out.qf_bitmap[qf_bloom_word(g, w24, out.qf_k)] |= qf_bits(g, h, out.qf_k);
@@ -1714,6 +1758,42 @@ void place_tables(CompiledSet& out, const DataStats* st) {
       }
       bent.push_back({bw, i << 8 | k});
     }
+  }
+  for (uint32_t x : used.cnt) out.qf_grams += x ? 1u : 0u;  // distinct probed grams
+  if (exact) {
+    std::vector<uint32_t> dg = egram;  // the distinct grams, in a fixed order
+    std::sort(dg.begin(), dg.end());
+    dg.erase(std::unique(dg.begin(), dg.end()), dg.end());
+    if (dg.size() > kQfExactMaxGrams) return false;
+    // 4-byte grams take their slot from their low three bytes: two that share those can
+    // never be apart
+    for (size_t j = 1; j < dg.size(); ++j)
+      if ((dg[j] & 0xFFFFFFu) == (dg[j - 1] & 0xFFFFFFu)) return false;
+    // a fixed sequence of odd 24-bit multipliers (the first is the Bloom probe's constant)
+    // until all grams land in distinct slots
+    std::vector<uint32_t> owner(kQfWords, 0u);  // slot -> try that last claimed it + 1
+    uint32_t mul = 0x9E3779u, found = 0;
+    for (uint32_t t = 1; t <= kQfExactTries && !found; ++t) {
+      bool ok = true;
+      for (size_t j = 0; j < dg.size() && ok; ++j) {
+        uint32_t& o = owner[qf_exact_slot(dg[j], mul)];
+        ok = o != t;
+        o = t;
+      }
+      if (ok) found = mul;
+      else mul = ((mul * 0x343FDu + 0x269EC3u) & 0xFFFFFFu) | 1u;
+    }
+    if (!found) return false;
+    out.qf_mul = found;
+    // unused slots: a value whose own slot is another one, so that no sample mapping to the
+    // slot can equal it (3-byte grams: its top byte is not the samples' 0xFF either)
+    for (uint32_t s = 0; s < kQfWords; ++s) {
+      uint32_t e = 0;
+      while (qf_exact_slot(e, found) == s) ++e;
+      out.qf_bitmap[s] = e;
+    }
+    for (uint32_t g : dg) out.qf_bitmap[qf_exact_slot(g, found)] = qf_exact_word(g, w24);
+    for (size_t j = 0; j < bent.size(); ++j) bent[j].first = qf_exact_slot(egram[j], found);
   }
   // needle bytes (loose needles are already stored OR 0x20), then 16-B entries per bucket
   std::vector<uint32_t> noff;
@@ -1747,6 +1827,7 @@ void place_tables(CompiledSet& out, const DataStats* st) {
       en[3] = w;
     }
   }
+  return true;
 }
 
 }  // namespace
@@ -1805,7 +1886,7 @@ PrefilterHits prefilter_hits(const CompiledSet& cs, const uint8_t* s, size_t n) 
     if (qf_sampled(p, S)) {
       ++r.probes;
       const uint32_t gq = (g | cs.qf_fold) & cs.qf_mask;
-      hit = qf_pass(cs.qf_bitmap.data(), gq, w24, cs.qf_k);
+      hit = qf_pass(cs.qf_bitmap.data(), gq, w24, cs.qf_k, cs.qf_mul);
       r.bitmap_hits += hit;
       if (cs.qf_k == kQfTwoLevel) r.pair_pass += (cs.qf_bitmap[qf_pair_word(gq & 0xFFFFu)] >> (gq & 31u)) & 1u;
     }
@@ -1815,7 +1896,7 @@ PrefilterHits prefilter_hits(const CompiledSet& cs, const uint8_t* s, size_t n) 
       r.anchor_hits += hit;
     }
     if (!hit) continue;
-    const uint32_t b = qf_bucket((g | cs.qf_fold) & cs.qf_mask, w24, cs.qf_k);
+    const uint32_t b = qf_bucket((g | cs.qf_fold) & cs.qf_mask, w24, cs.qf_k, cs.qf_mul);
     for (uint32_t e = cs.qf_head[b]; e < cs.qf_head[b + 1]; ++e) {
       const uint32_t* E = cs.qf_ent.data() + 4 * (size_t)e;
       const uint32_t m = E[1] & 0xFFFFu, k = (E[1] >> 16) & 0xFFu;
@@ -1862,14 +1943,14 @@ bool prefilter_match(const CompiledSet& cs, const uint8_t* s, size_t n, uint32_t
     bool hit = false;
     if (qf_sampled(p + 16 - phase % 16, S)) {
       const uint32_t gq = (g | cs.qf_fold) & cs.qf_mask;
-      hit = qf_pass(cs.qf_bitmap.data(), gq, cs.qf_q == 4 ? 24u : 0u, cs.qf_k);
+      hit = qf_pass(cs.qf_bitmap.data(), gq, cs.qf_q == 4 ? 24u : 0u, cs.qf_k, cs.qf_mul);
     }
     if (!hit && cs.qf_anc_on && ((uint32_t)s[p] | (cs.qf_anc_fold & 0xFFu)) == cs.qf_anc_byte)
       for (size_t j = 0; j + 1 < cs.qf_anc_pre.size() && !hit; j += 2)
         hit = ((g | cs.qf_fold) & cs.qf_anc_pre[j + 1]) == cs.qf_anc_pre[j];
     if (!hit) continue;
     g = (g | cs.qf_fold) & cs.qf_mask;
-    const uint32_t b = qf_bucket(g, cs.qf_q == 4 ? 24u : 0u, cs.qf_k);
+    const uint32_t b = qf_bucket(g, cs.qf_q == 4 ? 24u : 0u, cs.qf_k, cs.qf_mul);
     for (uint32_t e = cs.qf_head[b]; e < cs.qf_head[b + 1]; ++e) {
       const uint32_t* E = cs.qf_ent.data() + 4 * (size_t)e;
       const uint32_t m = E[1] & 0xFFFFu, k = (E[1] >> 16) & 0xFFu;

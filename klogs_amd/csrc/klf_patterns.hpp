@@ -112,8 +112,11 @@ struct CompiledSet {
   uint32_t qf_stride = 1;    // 1, 2, 4, 6 (grid) or 8
   uint32_t qf_fold = 0;      // 0x20202020 when some needle compares case-insensitively
   uint32_t qf_mask = ~0u;    // gram bytes (q < 4: low q bytes)
-  uint32_t qf_k = 3;         // bitmap bits per gram (qf_bits)
+  uint32_t qf_k = 3;         // bitmap bits per gram (qf_bits); kQfTwoLevel; kQfExact
+  uint32_t qf_mul = 0;       // kQfExact: the multiplier that gives every probed gram a slot of its own
+  uint32_t qf_grams = 0;     // distinct probed grams (diagnostics)
   std::vector<uint32_t> qf_bitmap;   // [kQfWords]: qf_k bits of word qf_word(qf_hash) per gram
+                                     // (kQfExact: the grams themselves, qf_exact_word at qf_exact_slot)
   std::vector<uint32_t> qf_head;     // [kQfWords + 1] bucket (= bitmap word) -> first entry
   std::vector<uint32_t> qf_ent;      // 16-B entries {needle dword offset, len | k << 16 | flags,
                                      //  regex, first needle dword}; k = offset of the gram

@@ -320,28 +320,30 @@ def debug_match(content: bytes, grep=(), match=()) -> bool:
 
 
 def debug_prefilter(content: bytes, grep=(), match=(), phase: int = 0):
-    """(match, {on, q, stride, needles, anchor}) of the prefiltered general matcher on the host
-    (anchor: the short needles' anchor byte, None when every needle is probed)."""
+    """(match, {on, q, stride, needles, anchor, k, mul}) of the prefiltered general matcher on the
+    host (anchor: the short needles' anchor byte, None when every needle is probed; k: bits per
+    gram, 5 two-level, 6 exact; mul: the exact probe's multiplier)."""
     arr, n, keep = _patterns(grep, match)
     m = C.c_int()
-    info = (C.c_uint32 * 5)()
+    info = (C.c_uint32 * 7)()
     buf = C.create_string_buffer(content, len(content) or 1)
     _check(_lib.klf_debug_prefilter(arr, n, buf, len(content), phase, C.byref(m), info))
     return bool(m.value), dict(on=bool(info[0]), q=info[1], stride=info[2], needles=info[3],
-                               anchor=(info[4] & 0xFF) if info[4] else None)
+                               anchor=(info[4] & 0xFF) if info[4] else None, k=info[5], mul=info[6])
 
 
 def debug_prefilter_hits(sample: bytes, data: bytes, grep=(), match=()):
     """The prefilter layout chosen on `sample`'s statistics and its work over `data` (host):
-    {stride, q, k, anchor, probes, bitmap_hits, anchor_hits, verified, pair_pass, layout}."""
+    {stride, q, k, anchor, probes, bitmap_hits, anchor_hits, verified, pair_pass, grams, mul, layout}
+    (grams: distinct probed grams; mul: the exact probe's multiplier, 0 for another kind)."""
     arr, n, keep = _patterns(grep, match)
-    out = (C.c_uint64 * 9)()
+    out = (C.c_uint64 * 11)()
     lay = C.create_string_buffer(256)
     sb = C.create_string_buffer(sample, len(sample) or 1)
     db = C.create_string_buffer(data, len(data) or 1)
     _check(_lib.klf_debug_prefilter_hits(arr, n, sb, len(sample), db, len(data), out, lay, 256))
     return dict(stride=out[0], q=out[1], k=out[2], anchor=(out[3] & 0xFF) if out[3] else None, probes=out[4],
-                bitmap_hits=out[5], anchor_hits=out[6], verified=out[7], pair_pass=out[8],
+                bitmap_hits=out[5], anchor_hits=out[6], verified=out[7], pair_pass=out[8], grams=out[9], mul=out[10],
                 layout=lay.value.decode())
 
 
