@@ -12,6 +12,7 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -21,9 +22,10 @@ ORACLE = ROOT / "oracle"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("KLF_OFFLOAD_ARCH", "gfx950")
 
-ENGINE_SRCS = ["klf_kernels.hip", "klf_engine.cpp", "klf_patterns.cpp"]
-ENGINE_HDRS = ["klf_kernels.hpp", "klf_patterns.hpp", "klf_ts.hpp", "klf_groupkey.hpp", "klf_fieldval.hpp",
-               "klf_copypool.hpp"]
+ENGINE_SRCS = ["klf_kernels.hip", "klf_analysis.hip", "klf_engine.cpp", "klf_analysis.cpp", "klf_patterns.cpp"]
+ENGINE_HDRS = ["klf_kernels.hpp", "klf_analysis.hpp", "klf_device.hpp", "klf_engine_impl.hpp", "klf_patterns.hpp",
+               "klf_ts.hpp", "klf_groupkey.hpp", "klf_fieldval.hpp", "klf_copypool.hpp"]
+MAX_COMPILE_JOBS = 16  # objects compiled at once, at most
 
 
 def _stale(out: Path, deps) -> bool:
@@ -43,7 +45,7 @@ def build_engine(force=False, quiet=True) -> Path:
     LIB.mkdir(parents=True, exist_ok=True)
     out = LIB / "libklf.so"
     hdrs = [CSRC / h for h in ENGINE_HDRS] + [ROOT / "include" / "klf.h", ROOT / "include" / "klf_debug.h"]
-    objs = []
+    objs, cmds = [], []
     for src in ENGINE_SRCS:
         s = CSRC / src
         o = LIB / (src.replace(".", "_") + ".o")
@@ -54,8 +56,12 @@ def build_engine(force=False, quiet=True) -> Path:
             else:
                 cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",
                        "-Wno-unused-function", "-c", s, "-o", o]
-            _run(cmd, quiet)
+            cmds.append(cmd)
         objs.append(o)
+    if cmds:  # the stale objects at once, one worker each
+        with ThreadPoolExecutor(max_workers=min(len(cmds), MAX_COMPILE_JOBS)) as pool:
+            for done in [pool.submit(_run, cmd, quiet) for cmd in cmds]:
+                done.result()
     if force or _stale(out, objs):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", out], quiet)
     return out

@@ -1,6 +1,8 @@
 // klf_engine.cpp — the C ABI of include/klf.h: staging, device workspace, the run,
 // result views.  One engine = one GPU = one HIP stream (one process per GPU; the
 // multi-GPU split happens above, in the host, by stream sharding — DESIGN.md §5).
+// The calls on a finished run that make an object or a table of their own (histogram,
+// timeline, groups, field statistics) are in klf_analysis.cpp.
 #include <hip/hip_runtime.h>
 
 #include <unistd.h>
@@ -22,49 +24,15 @@
 
 #include "../../include/klf.h"
 #include "../../include/klf_debug.h"
-#include "klf_copypool.hpp"
-#include "klf_fieldval.hpp"
-#include "klf_groupkey.hpp"
-#include "klf_kernels.hpp"
-#include "klf_patterns.hpp"
+#include "klf_engine_impl.hpp"
 #include "klf_ts.hpp"
 
-using klf::SegDesc;
-using klf::SegOut;
-
-namespace {
+using namespace klf_impl;
 
 // time spent growing device buffers (KLF_DIAG: the first run's allocation share)
-static std::atomic<uint64_t> g_alloc_ns{0};
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool borrowed = false;  // p lies in an engine's workspace block (not freed here)
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (p && !borrowed) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    borrowed = false;
-    size_t want = std::max<size_t>(bytes, 256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    const uint64_t ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    g_alloc_ns += ns;
-    static const bool diag = getenv("KLF_DIAG_ALLOC") != nullptr;
-    if (diag) fprintf(stderr, "[klf] alloc %zu B: %.1f us\n", want, ns / 1e3);
-    return e;
-  }
-  void release() {
-    if (p && !borrowed) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    borrowed = false;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
+std::atomic<uint64_t> klf_impl::g_alloc_ns{0};
+
+namespace {
 
 // An engine's first run maps its workspace buffers as one allocation (each hipMalloc costs
 // tens of us of host time, ~20 of them add up in a one-shot run): buffers not yet mapped
@@ -106,194 +74,9 @@ static hipError_t ensure_all(DevBuf& block, std::vector<DevBuf*>& users,
   return hipSuccess;
 }
 
-// Pinned host buffer (hipHostMalloc): per-run readbacks land here with one async DMA each
-// and a single stream sync (a pageable destination costs a staged copy and a wait per call).
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    release();
-    const size_t want = std::max<size_t>(bytes, 4096);
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
-
-struct klf_engine {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int num_cus = 256;
-  klf::CompiledSet cs;
-  std::string err;
-  uint64_t gen = 0;
-  // Staging (host path).  Each stream fills a pinned host chunk
-  // (hipHostMalloc, pooled across runs); a chunk that fills is DMA'd at once on the copy
-  // stream into a pooled 64 MiB device chunk, so the H2D overlaps the rest of the capture.
-  // klf_run DMAs the partly filled last chunk of every stream straight into the batch and
-  // one kernel (k_assemble) moves the device chunks into their places in the batch.
-  // Per-stream records are heap objects that never move (klf_stage on different ids runs
-  // concurrently while the table grows).
-  std::mutex mu;
-  struct StageChunk {
-    uint8_t* p = nullptr;
-    size_t used = 0;
-    bool pinned = false;
-  };
-  struct StagedStream {
-    std::vector<uint8_t*> dchunks;  // full chunks already DMA'd (device, kStageChunk each)
-    StageChunk cur;                 // pinned chunk being filled (p = null: none)
-    uint64_t len = 0;
-  };
-  std::vector<std::unique_ptr<StagedStream>> staged;
-  std::vector<StageChunk> chunk_pool;  // free pinned chunks (used = 0)
-  std::vector<uint8_t*> dchunk_pool;   // free device chunks
-  struct Inflight {
-    StageChunk c;
-    hipEvent_t ev;
-  };
-  std::deque<Inflight> inflight;       // pinned chunks whose H2D may still be running
-  std::vector<hipEvent_t> ev_pool;
-  hipStream_t copy_stream = nullptr;   // early H2D of full chunks
-  hipEvent_t copy_done = nullptr;
-  bool ran = false;                    // klf_run since the last klf_reset (stage -> ESTATE)
-  std::unique_ptr<klf::CopyPool> copier;  // started by the first klf_stage (device-resident runs never stage)
-  std::once_flag copier_once;
-  std::once_flag copy_stream_once;     // the copy stream: created by the first klf_stage / klf_run
-  hipError_t copy_stream_err = hipSuccess;
-  DevBuf d_asm;                        // k_assemble piece table
-  DevBuf d_scratch;                    // small query results (klf_result_last_unparsed)
-  DevBuf d_ac_out, d_ac_dict, d_pcount, d_pairs;  // per-pattern counts
-  uint32_t pairs_log2 = 20;            // (line, pattern) pair set: 2^20 entries, grows on overflow
-  uint32_t n_user = 0;                 // patterns as given to klf_open
-  // a set with an always-pattern beside others (CompiledSet::also_all_pending): the patterns,
-  // compiled in full on the first run that asks for per-pattern counts
-  std::vector<std::vector<uint8_t>> pend_pats;
-  std::vector<uint32_t> pend_kinds;
-  bool tune_later = true;
-  int counts_code = KLF_OK;            // that compile failed: counts unavailable (the filter is kAll's)
-  std::string counts_err;
-  // device pattern tables
-  DevBuf d_lit, d_ac_class, d_ac_next, d_ac_accept, d_rx_class, d_rx_b, d_rx_follow, d_rx_vec, d_rx_flags, d_rx_pre;
-  DevBuf d_qf_bitmap, d_qf_head, d_qf_ent, d_qf_nbytes, d_cand, d_rx_vec4, d_qhits, d_hslots, d_hist, d_hflat, d_qf_anc;
-  HostBuf h_hist;  // gram / byte statistics of the first batch (pinned readback)
-  uint32_t cand_cap = 1u << 22;  // NFA candidate queue (32 MiB); overflow -> k_match
-  uint64_t hits_cap_max = 1u << 26;  // prefilter hit list (512 MiB at most); overflow -> k_match
-  klf::DevPatterns dpats;
-  // workspace
-  std::vector<SegDesc> last_segs;  // tile_seg cache key
-  DevBuf d_tile_seg;
-  DevBuf d_cmap, d_cseg;
-  DevBuf d_block;  // the first run's workspace buffers (ensure_all), freed last
-  std::vector<DevBuf*> block_users;  // the buffers still mapped into d_block
-  DevBuf d_block2;  // the first run's line arrays, slot pool / records and output (sized after its sample)
-  std::vector<DevBuf*> block2_users;
-  DevBuf d_batch, d_segs, d_tstat, d_slots, d_pool, d_tile_base, d_bsum, d_cstatus, d_counters, d_line_off,
-      d_meta, d_bits, d_wpre, d_out, d_mpart, d_trec, d_truns, d_kbase;
-  // one-pass compaction (RunArgs::fuse): range table, extents, range states; d_out2 the
-  // contiguous device copy klf_result_device_out makes of a fused result on demand
-  DevBuf d_fext0, d_fext, d_frinfo, d_out2;
-  uint32_t fuse_range = 0, fuse_nranges = 0, fuse_next = 0;  // the layout d_fext0 was made for
-  std::vector<uint32_t> fuse_ext0;
-  // the segment table the extent table was built for: its own cache key (last_segs follows
-  // every run, fused or not, and a failed run may leave it behind d_fext0)
-  std::vector<SegDesc> fuse_segs;
-  uint64_t pool_cap = 1 << 20;
-  // lines per input byte of the last run (0: no run yet): sizes the line arrays of the next
-  // runs (the first run sizes them from its own tile index, between two launch phases)
-  double line_density = 0.0;
-  bool dense_tail_seen = false;  // a --tail run took the dense compaction (keep its run table)
-  HostBuf h_rb;  // run readback: the counters (kCtrBytes), the SegOut table, a one-pass run's extents
-  HostBuf h_stage;  // pinned staging of the prefilter tables (upload_prefilter)
-  HostBuf h_acblk;  // the automaton thread's tables (pinned), uploaded on the launch stream at the join
-  size_t ac_total = 0, ac_off[5] = {0, 0, 0, 0, 0}, ac_cap[5] = {0, 0, 0, 0, 0};
-  // The literals' Aho-Corasick automaton (deferred lines, the fallback matcher): klf_open
-  // starts a host thread that builds it and uploads it as one block (d_acblk, one
-  // synchronous copy); ensure_ac joins it before the first launch that may read it, so the
-  // build overlaps the first run's sampling and needle placement
-  std::thread ac_thread;
-  bool ac_pending = false;  // the automaton is built (or being built) but not yet uploaded
-  std::vector<std::vector<uint8_t>> ac_lits;
-  klf::AcTables ac_tabs;
-  hipError_t ac_err = hipSuccess;
-  DevBuf d_acblk;
-  hipEvent_t stage_ev = nullptr;  // the staged copies have drained
-  bool stage_ev_pending = false;
-  // KLF_GRAPH=1: small batches replay their launch sequence as a HIP graph (round 6): ~12
-  // launches cost ~35-45 us of host time.  Opt-in: measured on C1 (64 MiB) the run went
-  // 104 -> ~95 us, the device being the bound, while the first capture costs 5-7 ms (most
-  // of it creating cap_stream), which a short-lived engine pays in full.  A sequence is
-  // captured (on cap_stream: the engine's own stream may be the null stream) the second
-  // time the same arguments run; graph_off after a capture that failed.
-  hipStream_t cap_stream = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  std::vector<uint8_t> gkey, gprev;  // the captured arguments; the previous eager run's
-  bool graph_off = false;
-  hipEvent_t ev[11] = {};  // [7], [8]: k_scan's dispatch (hipExtLaunchKernel start / stop); [9], [10]: k_tcopy's; [6] unused
-  klf::RunArgs last_args{};  // arguments of the latest completed run (klf_retail)
-  // klf_regroup: the selection bitmap G' (the layout of d_bits) and the regroup kernels'
-  // chunk summaries; allocated by the first regroup, so a plain run pays nothing for them
-  DevBuf d_gbits, d_gsum;
-  // klf_result_histogram: the per-segment table and its pinned readback, the engine's own (no
-  // result's buffer is touched); allocated by the first histogram
-  DevBuf d_thist;
-  HostBuf h_thist;
-  // the latest run's global line index is still to be built (lazy index, dense path): the
-  // k_scatter launch that builds it
-  std::vector<klf::RunArgs> index_pending;
-  uint64_t last_gen = 0;     // gen of that run's result
-};
-
-struct klf_result {
-  klf_engine* e = nullptr;
-  uint64_t gen = 0;
-  uint32_t n_streams = 0;
-  std::vector<int64_t> seg_of;       // stream id -> segment (-1 = empty stream)
-  std::vector<SegOut> so;            // per segment
-  std::vector<uint64_t> seg_base;    // per segment (device byte offset)
-  bool has_bits = false;
-  bool grouped = false;              // selected over klf_regroup's bitmap (the engine's d_gbits)
-  uint64_t total_lines = 0, total_out = 0;
-  double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t ar_anchors = 0, ar_intervals = 0;  // a klf_around result: |A| and the merged intervals K,
-  double ar_build_ms = 0.0;                   // and the device time of building G' (part of ms[4])
-  uint32_t ev_mask = 0;              // the timing events the run recorded
-  int index_mode = KLF_INDEX_FULL;   // how much of the line index the run itself wrote
-  // lazily filled host copies
-  bool have_out = false, have_lines = false;
-  std::vector<uint8_t> out;
-  std::vector<uint64_t> line_off;
-  // [0] the match bitmap M, [1] a regrouped result's selection bitmap G'
-  struct HostBits {
-    bool have = false;
-    std::vector<uint32_t> bits;
-    std::vector<std::vector<uint8_t>> stream_bits;
-    std::vector<uint8_t> have_stream_bits;
-  } hbits[2];
-  // per-pattern counts (KLF_FILTER_PATTERN_COUNTS): [segment][compiled id]
-  bool counted = false, pcount_ok = false;
-  std::vector<uint32_t> pcount;
-  // a one-pass compaction run: each segment's output is the extents fx[2 k], fx[2 k + 1]
-  // (d_out offset, length) for k in [fx_first[s], fx_first[s + 1]); so[s].out_lo / out_hi
-  // are then the segment's place in the concatenated (host) output
-  bool fused = false, have_dev = false;
-  int compaction = KLF_COMPACT_GATHER;
-  std::vector<uint64_t> fx;
-  std::vector<uint32_t> fx_first;
-};
 
 // The run's counters and its per-stream records share one allocation (d_counters: the
 // counters, then the records from byte kCtrBytes on), so that one D2H copy reads both back.
@@ -302,7 +85,7 @@ static SegOut* segout_of(klf_engine* e) {
   return reinterpret_cast<SegOut*>(e->d_counters.as<uint8_t>() + kCtrBytes);
 }
 
-static int set_err(klf_engine* e, int code, const std::string& m) {
+int klf_impl::set_err(klf_engine* e, int code, const std::string& m) {
   if (e) e->err = m;
   return code;
 }
@@ -342,10 +125,9 @@ static void since_digits(int64_t sec, int64_t nsec, uint32_t out[6]) {
   out[4] = be(d[16], d[17], d[18], d[19]);  // n2..n5
   out[5] = be(d[20], d[21], '0', d[22]);    // n6 n7 pad n8
 }
-static int hip_err(klf_engine* e, hipError_t h, const char* where) {
+int klf_impl::hip_err(klf_engine* e, hipError_t h, const char* where) {
   return set_err(e, KLF_EHIP, std::string(where) + ": " + hipGetErrorString(h));
 }
-#define HIPCHK(e, x, where) do { hipError_t _h = (x); if (_h != hipSuccess) return hip_err(e, _h, where); } while (0)
 
 extern "C" const char* klf_strerror(int code) {
   switch (code) {
@@ -772,7 +554,6 @@ extern "C" void klf_close(klf_engine* e) {
 
 // ------------------------------------------------------------------------ staging ---
 
-static constexpr size_t kStageChunk = 64u << 20;  // pinned staging chunk = device chunk
 static constexpr size_t kMaxInflight = 8;         // pinned chunks with an H2D in flight (512 MiB)
 
 // The copy stream of the host staging path (and its event), made on first use: a
@@ -812,7 +593,7 @@ static void free_chunk(klf_engine::StageChunk& c) {
 
 // A free pinned chunk: the pool, else a chunk whose H2D has finished, else (with
 // kMaxInflight chunks in flight) the oldest one once its DMA is done, else a new one.
-static bool take_chunk(klf_engine* e, klf_engine::StageChunk* c) {
+bool klf_impl::take_chunk(klf_engine* e, klf_engine::StageChunk* c) {
   klf_engine::Inflight wait{};
   bool have_wait = false;
   {
@@ -1774,8 +1555,6 @@ extern "C" int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n,
   return run_device_impl(e, d_bytes, n, seg_base, lens, f, out);
 }
 
-static int ensure_index(klf_engine* e);
-
 // klf_retail (o null: over the bitmap the latest result was selected from), klf_regroup
 // (o: over G', built first from the run's match bitmap in d_bits) and klf_window (o and tw:
 // G' only when o asks for context or inversion, then cut by the time window when a bound is
@@ -1784,28 +1563,18 @@ static int ensure_index(klf_engine* e);
 static bool window_closed(const klf_window_opts* tw) {
   return tw->from.sec != KLF_TIME_MIN_SEC || tw->until.sec != KLF_TIME_MAX_SEC;
 }
-// Transforms and accessors of a finished run read the engine's workspace: only the latest
-// result still owns it.
-static int check_latest(klf_engine* e, const klf_result* r, const char* what) {
+int klf_impl::check_latest(klf_engine* e, const klf_result* r, const char* what) {
   if (r->gen != e->gen || e->last_gen != r->gen) return set_err(e, KLF_ESTATE, std::string(what) + ": not the latest run");
   return KLF_OK;
 }
-// The bitmap r was selected from (klf_result_group_bits): G' / G'', M, or none (no patterns:
-// the parsed lines).
-static const uint32_t* sel_bits(const klf_result* r) {
+const uint32_t* klf_impl::sel_bits(const klf_result* r) {
   return r->grouped ? r->e->d_gbits.as<uint32_t>() : r->has_bits ? r->e->d_bits.as<uint32_t>() : nullptr;
 }
-// What the kernels over r's selected lines read of its run (e->last_args: r is the latest).
-static klf::SelView sel_view(const klf_result* r) {
+klf::SelView klf_impl::sel_view(const klf_result* r) {
   const klf::RunArgs& a = r->e->last_args;
   const uint64_t nchunks = (r->total_lines + klf::kMatchChunk - 1) / klf::kMatchChunk;  // (<= cap_lines / kMatchChunk + 1)
   return {sel_bits(r), a.meta, a.line_off, a.bytes, a.segs, a.segout, (uint32_t)r->so.size(), a.cap_lines, nchunks};
 }
-
-// Builds klf_around's G' into e->d_gbits (sized by the caller) from the latest run's M; ms = the
-// build's device time, n / k = the anchors and their merged intervals.
-static int around_build(klf_engine* e, const klf_result* prev, const klf_around_opts* o, double& ms, uint64_t& n,
-                        uint64_t& k);
 
 static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
                        const char* what, const klf_window_opts* tw = nullptr, const klf_around_opts* ar = nullptr) {
@@ -2000,14 +1769,13 @@ extern "C" int klf_run(klf_engine* e, const klf_filter* f, klf_result** out) {
 
 // ---------------------------------------------------------------------- results ---
 
-static int check_result(klf_result* r, uint32_t id) {
+int klf_impl::check_result(klf_result* r, uint32_t id) {
   if (!r || id >= r->n_streams) return KLF_EINVAL;
   if (r->e->gen != r->gen) return KLF_ESTATE;  // workspace reused by a later run
   return KLF_OK;
 }
 
-// The latest run's global line index, built now if that run left it out (lazy index).
-static int ensure_index(klf_engine* e) {
+int klf_impl::ensure_index(klf_engine* e) {
   if (e->index_pending.empty()) return KLF_OK;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
   for (auto& x : e->index_pending) {
@@ -2070,7 +1838,7 @@ extern "C" int klf_result_stream(klf_result* r, uint32_t id, const uint8_t** byt
   return KLF_OK;
 }
 
-static bool write_all(int fd, const uint8_t* p, uint64_t n) {  // io.Copy's write loop
+bool klf_impl::write_all(int fd, const uint8_t* p, uint64_t n) {
   while (n) {
     const ssize_t k = ::write(fd, p, (size_t)std::min<uint64_t>(n, 1u << 30));
     if (k < 0) {
@@ -2097,30 +1865,14 @@ static bool write_all(int fd, const uint8_t* p, uint64_t n) {  // io.Copy's writ
 // in parallel and each file still sees one sequential write(2) sequence.  One descriptor
 // shared by several streams must see them in stream order: that case (and small outputs)
 // runs on the calling thread alone.
-namespace {
-// a stream's output: [lo, hi) of the concatenated output, in d_out as `parts` ({offset,
-// length}: one part, or a fused run's extents)
-struct WPiece {
-  uint64_t lo, hi;
-  int fd;
-  uint32_t id;
-  std::vector<std::pair<uint64_t, uint64_t>> parts;
-};
-
-struct WErr { std::atomic<int> id{-1}; int err = 0; std::string what; std::mutex mu; };
-
-// D2H each part of the stream's output in two halves of `buf` (double-buffered on `st`) and
-// write(2) each half to fd.  Returns false with `werr` set on the first failure.
-bool copy_part(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint64_t dlo, uint64_t n, uint8_t* buf,
-               uint64_t half, hipStream_t st, hipEvent_t ev[2], WErr& werr, uint64_t& total);
-bool copy_piece(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint8_t* buf, uint64_t half,
+static bool copy_piece(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint8_t* buf, uint64_t half,
                 hipStream_t st, hipEvent_t ev[2], WErr& werr, uint64_t& total) {
   for (const auto& pt : q.parts)
     if (pt.second && !copy_part(e, d_out, q, pt.first, pt.second, buf, half, st, ev, werr, total)) return false;
   return true;
 }
-bool copy_part(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint64_t dlo, uint64_t n, uint8_t* buf,
-               uint64_t half, hipStream_t st, hipEvent_t ev[2], WErr& werr, uint64_t& total) {
+bool klf_impl::copy_part(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint64_t dlo, uint64_t n, uint8_t* buf,
+                         uint64_t half, hipStream_t st, hipEvent_t ev[2], WErr& werr, uint64_t& total) {
   auto fail = [&](int err, const std::string& what) {
     int exp = -1;
     if (werr.id.compare_exchange_strong(exp, (int)q.id)) { werr.err = err; werr.what = what; }
@@ -2144,7 +1896,6 @@ bool copy_part(klf_engine* e, const uint8_t* d_out, const WPiece& q, uint64_t dl
   (void)e;
   return true;
 }
-}  // namespace
 
 extern "C" int klf_result_write(klf_result* r, const int* fds, uint32_t n_fds, uint64_t* written) {
   if (written) *written = 0;
@@ -2329,730 +2080,6 @@ extern "C" int klf_result_pattern_counts(klf_result* r, uint32_t id, uint64_t* c
     counts[u] = v;
   }
   return KLF_OK;
-}
-
-// ------------------------------------------ the scaffold of a call on a finished run ---
-
-namespace {
-// What a call (klf_result_histogram, _timeline, _groups, _field_stats) holds for its duration:
-// device buffers and the two events around its device time, given back on every return path.
-// `fn` is the calling function's name and `noun` what it makes, for the messages.
-struct CallScratch {
-  klf_engine* e;
-  const char *fn, *noun;
-  hipStream_t st;
-  std::vector<DevBuf> bufs;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  CallScratch(klf_engine* e_, const char* fn_, const char* noun_) : e(e_), fn(fn_), noun(noun_), st(e_->stream) {}
-  CallScratch(const CallScratch&) = delete;
-  ~CallScratch() {
-    for (DevBuf& b : bufs) b.release();
-    for (auto& x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-  // any buffer: the call's own or one of the object it returns
-  int alloc(DevBuf& b, size_t bytes, const char* what) {
-    const hipError_t h = b.ensure(bytes);
-    if (h == hipSuccess) return KLF_OK;
-    (void)hipGetLastError();
-    if (h == hipErrorOutOfMemory) return set_err(e, KLF_ENOMEM, std::string(fn) + ": alloc " + what);
-    return hip_err(e, h, what);
-  }
-  // a buffer of the call
-  template <class T>
-  int alloc(T*& p, size_t bytes, const char* what) {
-    DevBuf b;
-    const int rc = alloc(b, bytes, what);
-    p = b.as<T>();
-    bufs.push_back(b);
-    return rc;
-  }
-  std::string msg(const char* a, const char* b = "") const { return std::string(a) + noun + b; }
-  // The device time: start() before the first launch, then finish() after the last one, or
-  // stop() there and elapsed() behind a sync of the caller's own.
-  int start() {
-    for (auto& x : ev) HIPCHK(e, hipEventCreate(&x), msg("", " events").c_str());
-    HIPCHK(e, hipEventRecord(ev[0], st), msg("record ", " start").c_str());
-    return KLF_OK;
-  }
-  int stop() {
-    HIPCHK(e, hipEventRecord(ev[1], st), msg("record ", " end").c_str());
-    return KLF_OK;
-  }
-  int elapsed(double& ms) {
-    float f = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&f, ev[0], ev[1]), msg("", " timing").c_str());
-    ms = f;
-    return KLF_OK;
-  }
-  int finish(double& ms) {
-    if (int rc = stop()) return rc;
-    HIPCHK(e, hipStreamSynchronize(st), msg("sync ").c_str());
-    return elapsed(ms);
-  }
-};
-
-// The sort of n TlItems by their key (klf_kernels.hpp, SortArgs) as the host drives it:
-// prepare(n), the caller's kernel fills s.items[0], digits() makes the digit histograms and
-// reads them back (one copy, one sync), passes(p0, p1) runs the passes over the digits p0 ..
-// p1 - 1 that differ somewhere (one bin holding all n: nothing to move); sorted() is the buffer
-// the last pass wrote.  With n = 0 nothing is allocated, launched or read back.
-struct DeviceSort {
-  CallScratch& sc;
-  klf::SortArgs s{};
-  uint32_t cur = 0;
-  std::vector<uint64_t> dh;
-  explicit DeviceSort(CallScratch& sc_) : sc(sc_) {}
-  int prepare(uint64_t n) {
-    s.n = n;
-    if (!n) return KLF_OK;
-    for (auto& it : s.items)
-      if (int rc = sc.alloc(it, (size_t)n * sizeof(klf::TlItem), "sort items")) return rc;
-    return sc.alloc(s.dhist, (size_t)klf::kTlDigits * 256 * 8, "digit histograms");
-  }
-  int digits() {
-    if (!s.n) return KLF_OK;
-    dh.resize((size_t)klf::kTlDigits * 256);
-    HIPCHK(sc.e, klf::launch_sort_digits(s, sc.st, sc.e->num_cus), "launch k_tl_digits");
-    HIPCHK(sc.e, hipMemcpyAsync(dh.data(), s.dhist, dh.size() * 8, hipMemcpyDeviceToHost, sc.st), "D2H digit histograms");
-    HIPCHK(sc.e, hipStreamSynchronize(sc.st), "sync digit histograms");
-    return KLF_OK;
-  }
-  int passes(uint32_t p0, uint32_t p1) {
-    for (uint32_t p = p0; p < p1 && s.n; ++p) {
-      bool one_bin = false;
-      for (uint32_t d = 0; d < 256 && !one_bin; ++d) one_bin = dh[(size_t)p * 256 + d] == s.n;
-      if (one_bin) continue;
-      if (!s.bcnt) {
-        const size_t nblocks = (size_t)((s.n + klf::kTlSortBlock - 1) / klf::kTlSortBlock);
-        if (int rc = sc.alloc(s.bcnt, nblocks * 256 * 4, "block digit counts")) return rc;
-      }
-      HIPCHK(sc.e, klf::launch_sort_pass(s, p, cur, sc.st), "launch radix pass");
-      cur ^= 1u;
-    }
-    return KLF_OK;
-  }
-  klf::TlItem* sorted() const { return s.items[cur]; }
-};
-}  // namespace
-
-// klf_around's selection bitmap (SPEC.md S4g; the kernels: klf_kernels.hpp, ArArgs).
-static int around_build(klf_engine* e, const klf_result* prev, const klf_around_opts* o, double& ms, uint64_t& n,
-                        uint64_t& k) {
-  hipStream_t st = e->stream;
-  CallScratch sc(e, "klf_around", "around");
-  klf::TlArgs t{};
-  t.v = sel_view(prev);
-  t.v.bits_in = e->d_bits.as<uint32_t>();  // M: the anchors, whatever prev was selected from
-  uint32_t* gbits = e->d_gbits.as<uint32_t>();
-  if (int rc = sc.alloc(t.cbase, (t.v.nchunks + 1) * 8, "chunk bases")) return rc;
-  if (int rc = sc.start()) return rc;
-  // 1. anchors per chunk -> n
-  HIPCHK(e, klf::launch_tl_count(t.v, t.cbase, false, st, e->num_cus), "launch k_tl_count");
-  n = k = 0;
-  HIPCHK(e, hipMemcpyAsync(&n, t.cbase + t.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H anchor count");
-  HIPCHK(e, hipStreamSynchronize(st), "sync anchor count");
-  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_around: 2^32 or more anchors");
-  if (!n) {  // no anchor: a valid empty selection
-    HIPCHK(e, hipMemsetAsync(gbits, 0, (size_t)(t.v.cap_lines / 32 + 1) * 4, st), "zero selection bitmap");
-    return sc.finish(ms);
-  }
-  // 2. one item per anchor, 3. sorted by instant
-  t.n = n;
-  DeviceSort sort(sc);
-  if (int rc = sort.prepare(n)) return rc;
-  for (int i = 0; i < 2; ++i) t.items[i] = sort.s.items[i];
-  HIPCHK(e, klf::launch_tl_keys(t, false, st, e->num_cus), "launch k_tl_keys");
-  if (int rc = sort.digits()) return rc;
-  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
-  // 4. the merged intervals, 5. the parsed lines inside one
-  klf::ArArgs g{};
-  g.v = t.v;
-  g.v.bits_in = nullptr;
-  g.sorted = sort.sorted();
-  g.n = n;
-  const uint64_t span = o->before_ns + o->after_ns;  // < 2^63
-  g.before_sec = o->before_ns / 1000000000ull;
-  g.before_nsec = (uint32_t)(o->before_ns % 1000000000ull);
-  g.after_sec = o->after_ns / 1000000000ull;
-  g.after_nsec = (uint32_t)(o->after_ns % 1000000000ull);
-  g.span_sec = span / 1000000000ull;
-  g.span_nsec = (uint32_t)(span % 1000000000ull);
-  g.bits_out = gbits;
-  const size_t nb = (size_t)((n + klf::kArBlock - 1) / klf::kArBlock);
-  if (int rc = sc.alloc(g.bsum, (nb + 1) * 8, "head sums")) return rc;
-  HIPCHK(e, klf::launch_ar_heads(g, st), "launch k_ar_heads");
-  HIPCHK(e, hipMemcpyAsync(&k, g.bsum + nb, 8, hipMemcpyDeviceToHost, st), "D2H interval count");
-  HIPCHK(e, hipStreamSynchronize(st), "sync interval count");
-  if (!k || k > n) return set_err(e, KLF_EHIP, "klf_around: interval count out of range");  // (never: anchor 0 opens one)
-  g.k = k;
-  if (int rc = sc.alloc(g.iv, (size_t)k * sizeof(klf::ArIval), "intervals")) return rc;
-  HIPCHK(e, klf::launch_ar_build(g, st, e->num_cus), "launch k_ar_build");
-  return sc.finish(ms);
-}
-
-// Segment -> stream id.
-static std::vector<uint32_t> seg_streams(const klf_result* r) {
-  std::vector<uint32_t> v(r->so.size(), 0u);
-  for (uint32_t id = 0; id < r->n_streams; ++id)
-    if (r->seg_of[id] >= 0) v[(size_t)r->seg_of[id]] = id;
-  return v;
-}
-
-// The host copy of the n elements at d that a view of a returned object hands out: made by the
-// first call that asks, kept until the object is freed.
-template <class T>
-static int host_view(klf_engine* e, std::vector<T>& v, bool& have, const DevBuf& d, uint64_t n, const char* what) {
-  if (!have && n) {
-    try { v.resize((size_t)n); } catch (const std::bad_alloc&) { return KLF_ENOMEM; }
-    HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-    HIPCHK(e, hipMemcpy(v.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost), what);
-  }
-  have = true;
-  return KLF_OK;
-}
-
-extern "C" int klf_result_histogram(klf_result* r, const klf_hist_opts* o, uint64_t* counts, uint64_t* outside,
-                                    double* ms) {
-  if (!r || !o || !counts) return KLF_EINVAL;
-  klf_engine* e = r->e;
-  if (o->width_ns == 0 || o->n_buckets == 0 || o->n_buckets > KLF_HIST_MAX_BUCKETS)
-    return set_err(e, KLF_EINVAL, "klf_result_histogram: width_ns and n_buckets must be at least 1, n_buckets at most 65536");
-  if (o->width_ns > (uint64_t)INT64_MAX / o->n_buckets)
-    return set_err(e, KLF_EINVAL, "klf_result_histogram: n_buckets * width_ns must stay below 2^63");
-  if (o->origin.nsec < 0 || o->origin.nsec >= 1000000000)
-    return set_err(e, KLF_EINVAL, "klf_result_histogram: nsec outside [0, 1e9)");
-  if (o->flags || o->origin._reserved)
-    return set_err(e, KLF_EINVAL, "klf_result_histogram: unknown flag bits or a non-zero _reserved");
-  if (int rc = check_latest(e, r, "klf_result_histogram")) return rc;
-  const uint32_t nsegs = (uint32_t)r->so.size(), nb = o->n_buckets;
-  const uint64_t row = (uint64_t)nb + 2;
-  if ((uint64_t)nsegs * row > (1ull << 24))
-    return set_err(e, KLF_ETOOBIG, "klf_result_histogram: non-empty streams * (n_buckets + 2) exceeds 2^24");
-  if (ms) *ms = 0.0;
-  memset(counts, 0, (size_t)r->n_streams * nb * 8);
-  if (outside) memset(outside, 0, (size_t)r->n_streams * 2 * 8);
-  if (!nsegs) return KLF_OK;
-  if (int rc = ensure_index(e)) return rc;
-  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  const uint64_t span = o->width_ns * nb;  // ns, < 2^63
-  klf::HistArgs g{};
-  g.v = sel_view(r);
-  g.n_buckets = nb;
-  g.org_sec = o->origin.sec;
-  g.org_nsec = o->origin.nsec;
-  int64_t end_nsec = o->origin.nsec + (int64_t)(span % 1000000000ull), carry = 0;
-  if (end_nsec >= 1000000000) { end_nsec -= 1000000000; carry = 1; }
-  g.end_nsec = (int32_t)end_nsec;
-  g.end_open = __builtin_add_overflow(o->origin.sec, (int64_t)(span / 1000000000ull) + carry, &g.end_sec) ? 1u : 0u;
-  g.width_ns = o->width_ns;
-  g.width_s = o->width_ns % 1000000000ull == 0 && span / 1000000000ull < (1ull << 32)
-                  ? (uint32_t)(o->width_ns / 1000000000ull) : 0u;
-  const size_t tbytes = (size_t)nsegs * row * 8;
-  HIPCHK(e, e->d_thist.ensure(tbytes), "alloc histogram table");
-  HIPCHK(e, e->h_thist.ensure(tbytes), "alloc histogram readback");
-  g.table = e->d_thist.as<uint64_t>();
-  CallScratch sc(e, "klf_result_histogram", "histogram");  // (its events alone: the table is the engine's)
-  if (int rc = sc.start()) return rc;
-  HIPCHK(e, klf::launch_hist(g, e->stream, e->num_cus), "launch k_hist");
-  if (int rc = sc.stop()) return rc;
-  HIPCHK(e, hipMemcpyAsync(e->h_thist.p, e->d_thist.p, tbytes, hipMemcpyDeviceToHost, e->stream), "D2H histogram");
-  HIPCHK(e, hipStreamSynchronize(e->stream), "sync histogram");
-  if (ms)
-    if (int rc = sc.elapsed(*ms)) return rc;
-  const uint64_t* tab = e->h_thist.as<uint64_t>();
-  for (uint32_t id = 0; id < r->n_streams; ++id) {
-    const int64_t s = r->seg_of[id];
-    if (s < 0) continue;
-    memcpy(counts + (size_t)id * nb, tab + (size_t)s * row, (size_t)nb * 8);
-    if (outside) memcpy(outside + (size_t)id * 2, tab + (size_t)s * row + nb, 16);
-  }
-  return KLF_OK;
-}
-
-// ------------------------------------------------------------- merged timeline ---
-
-// A timeline owns what it returns: the entry records and the merged bytes on the device, and
-// their host copies once a view asked for them.  Nothing of the engine's workspace is kept.
-struct klf_timeline {
-  klf_engine* e = nullptr;
-  uint64_t n = 0, len = 0;
-  double ms = 0.0;
-  DevBuf d_entries, d_bytes;
-  bool have_entries = false, have_bytes = false;
-  std::vector<klf_timeline_entry> entries;
-  std::vector<uint8_t> bytes;
-  ~klf_timeline() {
-    d_entries.release();
-    d_bytes.release();
-  }
-};
-static_assert(sizeof(klf_timeline_entry) == sizeof(klf::TlEntry) && sizeof(klf_timeline_entry) == 32,
-              "klf_timeline_entry is the kernels' TlEntry");
-
-extern "C" int klf_result_timeline(klf_result* r, const klf_timeline_opts* o, klf_timeline** out) {
-  if (!r || !o || !out) return KLF_EINVAL;
-  klf_engine* e = r->e;
-  if ((o->flags & ~KLF_TIMELINE_TIMESTAMPS) || o->_reserved)
-    return set_err(e, KLF_EINVAL, "klf_result_timeline: unknown flag bits or a non-zero _reserved");
-  if (o->tags && !o->tag_off) return set_err(e, KLF_EINVAL, "klf_result_timeline: tags without tag_off");
-  if (o->tags)
-    for (uint32_t i = 0; i < r->n_streams; ++i) {
-      if (o->tag_off[i + 1] < o->tag_off[i]) return set_err(e, KLF_EINVAL, "klf_result_timeline: tag_off must ascend");
-      if (o->tag_off[i + 1] - o->tag_off[i] > KLF_TIMELINE_MAX_TAG)
-        return set_err(e, KLF_EINVAL, "klf_result_timeline: a tag is longer than KLF_TIMELINE_MAX_TAG");
-    }
-  if (int rc = check_latest(e, r, "klf_result_timeline")) return rc;
-  std::unique_ptr<klf_timeline> t(new (std::nothrow) klf_timeline());
-  if (!t) return KLF_ENOMEM;
-  t->e = e;
-  const uint32_t nsegs = (uint32_t)r->so.size();
-  if (!nsegs) {  // no stream has bytes
-    *out = t.release();
-    return KLF_OK;
-  }
-  if (int rc = ensure_index(e)) return rc;
-  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  hipStream_t st = e->stream;
-  CallScratch sc(e, "klf_result_timeline", "timeline");
-  klf::TlArgs g{};
-  g.v = sel_view(r);
-  g.timestamps = (o->flags & KLF_TIMELINE_TIMESTAMPS) ? 1u : 0u;
-  // per segment: its stream id and its tag
-  const std::vector<uint32_t> streams = seg_streams(r);
-  std::vector<uint32_t> segtab((size_t)nsegs * 3, 0u);
-  for (uint32_t s = 0; s < nsegs; ++s) {
-    const uint32_t id = segtab[3 * (size_t)s] = streams[s];
-    if (o->tags) {
-      segtab[3 * (size_t)s + 1] = o->tag_off[id];
-      segtab[3 * (size_t)s + 2] = o->tag_off[id + 1] - o->tag_off[id];
-    }
-  }
-  const uint32_t tag_bytes = o->tags ? o->tag_off[r->n_streams] : 0u;
-  uint32_t* d_segtab = nullptr;
-  if (int rc = sc.alloc(d_segtab, segtab.size() * 4, "segment table")) return rc;
-  HIPCHK(e, hipMemcpyAsync(d_segtab, segtab.data(), segtab.size() * 4, hipMemcpyHostToDevice, st), "H2D segment table");
-  g.segtab = d_segtab;
-  if (tag_bytes) {
-    uint8_t* d_tags = nullptr;
-    if (int rc = sc.alloc(d_tags, tag_bytes, "tags")) return rc;
-    HIPCHK(e, hipMemcpyAsync(d_tags, o->tags, tag_bytes, hipMemcpyHostToDevice, st), "H2D tags");
-    g.tags = d_tags;
-  }
-  if (int rc = sc.alloc(g.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
-  if (int rc = sc.start()) return rc;
-  // 1. E lines per chunk -> n
-  HIPCHK(e, klf::launch_tl_count(g.v, g.cbase, true, st, e->num_cus), "launch k_tl_count");
-  uint64_t n = 0;
-  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H timeline size");
-  HIPCHK(e, hipStreamSynchronize(st), "sync timeline size");
-  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_timeline: more than 2^32 - 1 entries");
-  if (!n) {
-    if (int rc = sc.finish(t->ms)) return rc;
-    *out = t.release();
-    return KLF_OK;
-  }
-  g.n = n;
-  // 2. keys, 3. the sort
-  DeviceSort sort(sc);
-  if (int rc = sort.prepare(n)) return rc;
-  for (int k = 0; k < 2; ++k) g.items[k] = sort.s.items[k];
-  if (int rc = sc.alloc(g.side, n * sizeof(klf::TlSide), "side records")) return rc;
-  HIPCHK(e, klf::launch_tl_keys(g, true, st, e->num_cus), "launch k_tl_keys");
-  if (int rc = sort.digits()) return rc;
-  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
-  // 4. rendered lengths -> offsets, entries, bytes
-  const size_t pblocks = (size_t)((n + klf::kTlPlanBlock - 1) / klf::kTlPlanBlock);
-  if (int rc = sc.alloc(g.psum, (pblocks + 1) * 8, "block sums")) return rc;
-  HIPCHK(e, klf::launch_tl_plan(g, sort.cur, st), "launch k_tl_plan");
-  uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, g.psum + pblocks, 8, hipMemcpyDeviceToHost, st), "D2H merged length");
-  HIPCHK(e, hipStreamSynchronize(st), "sync merged length");
-  if (int rc = sc.alloc(t->d_entries, n * sizeof(klf::TlEntry), "entries")) return rc;
-  if (int rc = sc.alloc(t->d_bytes, total + 16, "merged bytes")) return rc;
-  g.entries = t->d_entries.as<klf::TlEntry>();
-  g.out = t->d_bytes.as<uint8_t>();
-  HIPCHK(e, klf::launch_tl_copy(g, sort.cur, st), "launch k_tl_copy");
-  if (int rc = sc.finish(t->ms)) return rc;
-  t->n = n;
-  t->len = total;
-  *out = t.release();
-  return KLF_OK;
-}
-
-extern "C" int klf_timeline_entries(klf_timeline* t, const klf_timeline_entry** ent, uint64_t* n) {
-  if (!t || !ent || !n) return KLF_EINVAL;
-  if (int rc = host_view(t->e, t->entries, t->have_entries, t->d_entries, t->n, "D2H timeline entries")) return rc;
-  *ent = t->entries.data();
-  *n = t->n;
-  return KLF_OK;
-}
-
-extern "C" int klf_timeline_bytes(klf_timeline* t, const uint8_t** bytes, uint64_t* len) {
-  if (!t || !len) return KLF_EINVAL;
-  *len = t->len;
-  if (!bytes) return KLF_OK;
-  if (int rc = host_view(t->e, t->bytes, t->have_bytes, t->d_bytes, t->len, "D2H merged bytes")) return rc;
-  *bytes = t->bytes.data();
-  return KLF_OK;
-}
-
-// klf_result_write's path for one descriptor: a pinned chunk from the staging pool, D2H in two
-// halves of it with the next half in flight while the current one is written.
-extern "C" int klf_timeline_write(klf_timeline* t, int fd, uint64_t* written) {
-  if (written) *written = 0;
-  if (!t || fd < 0) return KLF_EINVAL;
-  klf_engine* e = t->e;
-  if (!t->len) return KLF_OK;
-  if (t->have_bytes) {  // already on the host
-    if (!write_all(fd, t->bytes.data(), t->len))
-      return set_err(e, KLF_EIO, std::string("write merged timeline: ") + strerror(errno));
-    if (written) *written = t->len;
-    return KLF_OK;
-  }
-  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  klf_engine::StageChunk c;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const bool ok = take_chunk(e, &c) && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-                  hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) == hipSuccess;
-  WErr werr;
-  uint64_t total = 0;
-  const WPiece q{0, t->len, fd, 0, {}};
-  if (ok) (void)copy_part(e, t->d_bytes.as<uint8_t>(), q, 0, t->len, c.p, kStageChunk / 2, st, ev, werr, total);
-  if (st) (void)hipStreamSynchronize(st);  // no DMA into a chunk handed back below
-  for (auto& x : ev)
-    if (x) (void)hipEventDestroy(x);
-  if (st) (void)hipStreamDestroy(st);
-  if (c.p) {
-    std::lock_guard<std::mutex> lk(e->mu);
-    c.used = 0;
-    e->chunk_pool.push_back(c);
-  }
-  if (written) *written = total;
-  if (!ok) return set_err(e, KLF_ENOMEM, "klf_timeline_write: setup (pinned chunk / HIP stream)");
-  if (werr.id.load() >= 0)
-    return set_err(e, KLF_EIO, "write merged timeline: " + werr.what + (werr.err ? std::string(": ") + strerror(werr.err) : std::string()));
-  return KLF_OK;
-}
-
-extern "C" int klf_timeline_ms(const klf_timeline* t, double* ms) {
-  if (!t || !ms) return KLF_EINVAL;
-  *ms = t->ms;
-  return KLF_OK;
-}
-
-extern "C" void klf_timeline_free(klf_timeline* t) { delete t; }
-
-// -------------------------------------------------------------- grouped counts ---
-
-// A groups object owns what it returns, like a timeline: the entry records and the key bytes
-// on the device, and their host copies once a view asked for them.
-struct klf_groups {
-  klf_engine* e = nullptr;
-  uint64_t n = 0, key_bytes = 0, n_groups = 0, n_lines = 0;
-  double ms = 0.0;
-  DevBuf d_entries, d_keys;
-  bool have_entries = false, have_keys = false;
-  std::vector<klf_group_entry> entries;
-  std::vector<uint8_t> keys;
-  ~klf_groups() {
-    d_entries.release();
-    d_keys.release();
-  }
-};
-static_assert(sizeof(klf_group_entry) == sizeof(klf::GrEntry) && sizeof(klf_group_entry) == 48 &&
-                  sizeof(klf_groups_opts) == 16,
-              "klf_group_entry is the kernels' GrEntry");
-static_assert(KLF_GROUPS_MASK_DIGITS == klf::kGroupsMaskDigits, "one flag value for the host helper and the kernels");
-
-// KLF_GROUPS_HASH_BITS (1..64, a test hook: DESIGN.md): the low bits of the hash that are used.
-static uint32_t groups_hash_bits() {
-  const char* s = getenv("KLF_GROUPS_HASH_BITS");
-  if (!s || !*s) return 64;
-  char* end = nullptr;
-  const long v = strtol(s, &end, 10);
-  return (*end || v < 1 || v > 64) ? 64u : (uint32_t)v;
-}
-
-extern "C" int klf_result_groups(klf_result* r, const klf_groups_opts* o, klf_groups** out) {
-  if (!r || !o || !out) return KLF_EINVAL;
-  klf_engine* e = r->e;
-  if (o->top == 0 || o->top > KLF_GROUPS_MAX_TOP)
-    return set_err(e, KLF_EINVAL, "klf_result_groups: top must be 1 .. 65536");
-  if (o->max_groups > KLF_GROUPS_MAX_GROUPS)
-    return set_err(e, KLF_EINVAL, "klf_result_groups: max_groups above 2^26");
-  if (o->flags & ~KLF_GROUPS_MASK_DIGITS) return set_err(e, KLF_EINVAL, "klf_result_groups: unknown flag bits");
-  if (int rc = check_latest(e, r, "klf_result_groups")) return rc;
-  std::unique_ptr<klf_groups> t(new (std::nothrow) klf_groups());
-  if (!t) return KLF_ENOMEM;
-  t->e = e;
-  const uint32_t nsegs = (uint32_t)r->so.size();
-  if (!nsegs) {  // no stream has bytes
-    *out = t.release();
-    return KLF_OK;
-  }
-  if (r->total_lines >> klf::kGrLineBits)
-    return set_err(e, KLF_ETOOBIG, "klf_result_groups: 2^40 or more lines in the run");
-  if (int rc = ensure_index(e)) return rc;
-  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  hipStream_t st = e->stream;
-  CallScratch sc(e, "klf_result_groups", "groups");
-  klf::GroupArgs g{};
-  g.v = sel_view(r);
-  g.max_key = o->max_key;
-  g.flags = o->flags;
-  g.hash_bits = groups_hash_bits();
-  // P = pow2 >= 2 * the keys the table must hold: max_groups, or the run's lines when fewer
-  const uint64_t max_groups = o->max_groups ? o->max_groups : (1ull << 20);
-  const uint64_t hold = std::min<uint64_t>(max_groups, r->total_lines);
-  g.table_log2 = 6;
-  while ((1ull << g.table_log2) < 2 * hold) ++g.table_log2;  // (<= 27)
-  const uint64_t P = 1ull << g.table_log2;
-  const size_t cblocks = (size_t)((P + klf::kGrCountBlock - 1) / klf::kGrCountBlock);
-  if (int rc = sc.alloc(g.table, (size_t)(4 * P + 2) * 8, "hash table")) return rc;
-  if (int rc = sc.alloc(g.bsum, (cblocks + 1) * 8, "slot sums")) return rc;
-  if (int rc = sc.start()) return rc;
-  // 1. every line of H into the table; the occupied slots -> n_groups
-  HIPCHK(e, klf::launch_gr_insert(g, st, e->num_cus), "launch k_gr_insert");
-  HIPCHK(e, klf::launch_gr_count(g, st), "launch k_gr_count");
-  uint64_t stats[2] = {0, 0}, n_groups = 0;
-  HIPCHK(e, hipMemcpyAsync(stats, g.table + 4 * P, 16, hipMemcpyDeviceToHost, st), "D2H groups totals");
-  HIPCHK(e, hipMemcpyAsync(&n_groups, g.bsum + cblocks, 8, hipMemcpyDeviceToHost, st), "D2H groups count");
-  HIPCHK(e, hipStreamSynchronize(st), "sync groups count");
-  if (stats[1] || n_groups > max_groups)  // (a full table holds P > max_groups keys: the same answer)
-    return set_err(e, KLF_ETOOBIG, "klf_result_groups: more than max_groups = " + std::to_string(max_groups) +
-                                       " distinct keys; mask digits (KLF_GROUPS_MASK_DIGITS), cut the key (max_key) or "
-                                       "raise max_groups");
-  t->n_lines = stats[0];
-  t->n_groups = n_groups;
-  if (!n_groups) {
-    if (int rc = sc.finish(t->ms)) return rc;
-    *out = t.release();
-    return KLF_OK;
-  }
-  // 2. one item per group, sorted by (count desc, first asc)
-  g.n_groups = n_groups;
-  DeviceSort sort(sc);
-  if (int rc = sort.prepare(n_groups)) return rc;
-  g.items = sort.s.items[0];
-  if (int rc = sc.alloc(g.gslot, n_groups * 4, "item slots")) return rc;
-  HIPCHK(e, klf::launch_gr_fill(g, st), "launch k_gr_fill");
-  if (int rc = sort.digits()) return rc;
-  if (int rc = sort.passes(0, klf::kTlDigits)) return rc;
-  // 3. the first `top` groups: key lengths -> offsets, then the records and the key bytes
-  g.top = (uint32_t)std::min<uint64_t>(o->top, n_groups);
-  const std::vector<uint32_t> segstream = seg_streams(r);
-  uint32_t* d_segstream = nullptr;
-  if (int rc = sc.alloc(d_segstream, (size_t)nsegs * 4, "segment table")) return rc;
-  HIPCHK(e, hipMemcpyAsync(d_segstream, segstream.data(), (size_t)nsegs * 4, hipMemcpyHostToDevice, st), "H2D segment table");
-  g.segstream = d_segstream;
-  if (int rc = sc.alloc(g.klen, ((size_t)g.top + 1) * 8, "key lengths")) return rc;
-  HIPCHK(e, klf::launch_gr_plan(g, sort.sorted(), st), "launch k_gr_plan");
-  uint64_t total = 0;
-  HIPCHK(e, hipMemcpyAsync(&total, g.klen + g.top, 8, hipMemcpyDeviceToHost, st), "D2H key bytes");
-  HIPCHK(e, hipStreamSynchronize(st), "sync key bytes");
-  if (int rc = sc.alloc(t->d_entries, (size_t)g.top * sizeof(klf::GrEntry), "entries")) return rc;
-  if (int rc = sc.alloc(t->d_keys, total + 16, "key bytes")) return rc;
-  g.entries = t->d_entries.as<klf::GrEntry>();
-  g.keys = t->d_keys.as<uint8_t>();
-  HIPCHK(e, klf::launch_gr_render(g, sort.sorted(), st), "launch k_gr_render");
-  if (int rc = sc.finish(t->ms)) return rc;
-  t->n = g.top;
-  t->key_bytes = total;
-  *out = t.release();
-  return KLF_OK;
-}
-
-extern "C" int klf_groups_entries(klf_groups* t, const klf_group_entry** ent, uint64_t* n) {
-  if (!t || !ent || !n) return KLF_EINVAL;
-  if (int rc = host_view(t->e, t->entries, t->have_entries, t->d_entries, t->n, "D2H group entries")) return rc;
-  *ent = t->entries.data();
-  *n = t->n;
-  return KLF_OK;
-}
-
-extern "C" int klf_groups_keys(klf_groups* t, const uint8_t** bytes, uint64_t* len) {
-  if (!t || !bytes || !len) return KLF_EINVAL;
-  if (int rc = host_view(t->e, t->keys, t->have_keys, t->d_keys, t->key_bytes, "D2H group keys")) return rc;
-  *bytes = t->keys.data();
-  *len = t->key_bytes;
-  return KLF_OK;
-}
-
-extern "C" int klf_groups_totals(const klf_groups* t, uint64_t* n_groups, uint64_t* n_lines) {
-  if (!t) return KLF_EINVAL;
-  if (n_groups) *n_groups = t->n_groups;
-  if (n_lines) *n_lines = t->n_lines;
-  return KLF_OK;
-}
-
-extern "C" int klf_groups_ms(const klf_groups* t, double* ms) {
-  if (!t || !ms) return KLF_EINVAL;
-  *ms = t->ms;
-  return KLF_OK;
-}
-
-extern "C" void klf_groups_free(klf_groups* t) { delete t; }
-
-extern "C" int klf_group_key(const uint8_t* content, size_t len, uint32_t max_key, uint32_t flags, uint8_t* out,
-                             size_t cap, size_t* n) {
-  if (n) *n = 0;
-  if ((!content && len) || (!out && cap) || (flags & ~KLF_GROUPS_MASK_DIGITS)) return KLF_EINVAL;
-  const size_t span = (size_t)klf::group_key_span(len, max_key);
-  size_t need = 0;
-  {
-    klf::GroupKeyNorm nm(flags);
-    uint8_t c;
-    for (size_t i = 0; i < span; ++i) need += nm.step(content[i], c) ? 1 : 0;
-  }
-  if (n) *n = need;
-  if (need > cap) return KLF_EINVAL;
-  klf::GroupKeyNorm nm(flags);
-  size_t k = 0;
-  for (size_t i = 0; i < span; ++i) {
-    uint8_t c;
-    if (nm.step(content[i], c)) out[k++] = c;
-  }
-  return KLF_OK;
-}
-
-// ------------------------------------------------------- numeric field statistics ---
-
-static_assert(sizeof(klf_field_opts) == 32 && sizeof(klf_field_row) == 80, "klf_field_opts / klf_field_row layout");
-static_assert(KLF_FIELD_DURATION == klf::kFieldDuration && KLF_FIELD_MAX_KEY == klf::kFieldMaxKey &&
-                  KLF_FIELD_MAX_KEY == klf::kFsMaxKey && KLF_FIELD_MAX_QUANTILES == klf::kFsMaxQuantiles &&
-                  KLF_FIELD_HIT == klf::kFieldHit && KLF_FIELD_MISS == klf::kFieldMiss && KLF_FIELD_BAD == klf::kFieldBad,
-              "one set of values for the host helper and the kernels");
-
-static bool field_opts_ok(const uint8_t* key, uint32_t key_len, uint32_t decimals, uint32_t flags) {
-  return key && key_len >= 1 && key_len <= KLF_FIELD_MAX_KEY && !(flags & ~KLF_FIELD_DURATION) && decimals <= 9 &&
-         !((flags & KLF_FIELD_DURATION) && decimals);
-}
-
-extern "C" int klf_result_field_stats(klf_result* r, const klf_field_opts* o, klf_field_row* rows, int64_t* qvals,
-                                      double* ms) {
-  if (!r || !o || !rows) return KLF_EINVAL;
-  klf_engine* e = r->e;
-  if (!field_opts_ok(o->key, o->key_len, o->decimals, o->flags))
-    return set_err(e, KLF_EINVAL, "klf_result_field_stats: key of 1 .. 64 bytes, decimals 0 .. 9 (0 with "
-                                  "KLF_FIELD_DURATION), no unknown flag bits");
-  if (o->n_quantiles > KLF_FIELD_MAX_QUANTILES || (o->n_quantiles && (!o->quantiles || !qvals)))
-    return set_err(e, KLF_EINVAL, "klf_result_field_stats: at most 16 quantiles, with their arrays");
-  for (uint32_t k = 0; k < o->n_quantiles; ++k)
-    if (o->quantiles[k] > 10000) return set_err(e, KLF_EINVAL, "klf_result_field_stats: a quantile above 10000");
-  if (int rc = check_latest(e, r, "klf_result_field_stats")) return rc;
-  const uint32_t nsegs = (uint32_t)r->so.size(), nq = o->n_quantiles, nrows = r->n_streams + 1;
-  if (ms) *ms = 0.0;
-  for (uint32_t i = 0; i < nrows; ++i) {
-    rows[i] = klf_field_row{};
-    rows[i].min_line = rows[i].max_line = UINT64_MAX;
-    rows[i].min_stream = rows[i].max_stream = UINT32_MAX;
-  }
-  if (nq) memset(qvals, 0, (size_t)nrows * nq * 8);
-  if (!nsegs) return KLF_OK;  // no stream has bytes
-  if (nsegs >> 30) return set_err(e, KLF_ETOOBIG, "klf_result_field_stats: 2^30 or more streams with bytes");
-  if (int rc = ensure_index(e)) return rc;
-  HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
-  hipStream_t st = e->stream;
-  CallScratch sc(e, "klf_result_field_stats", "field statistics");
-  klf::FieldArgs g{};
-  g.v = sel_view(r);
-  memcpy(g.key, o->key, o->key_len);
-  g.key_len = o->key_len;
-  g.decimals = o->decimals;
-  g.flags = o->flags;
-  g.n_q = nq;
-  for (uint32_t k = 0; k < nq; ++k) g.q[k] = o->quantiles[k];
-  if (int rc = sc.alloc(g.cbase, (g.v.nchunks + 1) * 8, "chunk bases")) return rc;
-  if (int rc = sc.alloc(g.hbase, (g.v.nchunks + 1) * 8, "chunk hit bases")) return rc;
-  // the result block: the table, the segments' hit prefix, the rows, the quantile values
-  const size_t tab_w = (size_t)klf::kFsTabRows * nsegs, hpre_w = (size_t)nsegs + 1,
-               rows_w = ((size_t)nsegs + 1) * (sizeof(klf::FsRow) / 8), qv_w = ((size_t)nsegs + 1) * nq;
-  const size_t res_w = tab_w + hpre_w + rows_w + qv_w;
-  if (int rc = sc.alloc(g.tab, res_w * 8, "result block")) return rc;
-  g.hpre = g.tab + tab_w;
-  g.rows = reinterpret_cast<klf::FsRow*>(g.hpre + hpre_w);
-  g.qv = reinterpret_cast<int64_t*>(g.hpre + hpre_w + rows_w);
-  if (int rc = sc.start()) return rc;
-  // 1. H lines per chunk -> n
-  HIPCHK(e, klf::launch_tl_count(g.v, g.cbase, false, st, e->num_cus), "launch k_tl_count");
-  uint64_t n = 0;
-  HIPCHK(e, hipMemcpyAsync(&n, g.cbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics size");
-  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics size");
-  if (n > 0xFFFFFFFFull) return set_err(e, KLF_ETOOBIG, "klf_result_field_stats: 2^32 or more lines in the selection");
-  g.n = n;
-  // 2. every line's class and value; per segment the counts and the sum; the hits per chunk -> n_hits
-  if (int rc = sc.alloc(g.val, (size_t)n * 8, "values")) return rc;
-  if (int rc = sc.alloc(g.cs, (size_t)n * 4, "classes")) return rc;
-  HIPCHK(e, klf::launch_fs_extract(g, st, e->num_cus), "launch k_fs_extract");
-  uint64_t n_hits = 0;
-  HIPCHK(e, hipMemcpyAsync(&n_hits, g.hbase + g.v.nchunks, 8, hipMemcpyDeviceToHost, st), "D2H field statistics hits");
-  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics hits");
-  g.n_hits = n_hits;
-  // 3. the hits as sort items; value order -> the all-streams row; (segment, value) order -> the rest
-  DeviceSort sort(sc);
-  if (int rc = sort.prepare(n_hits)) return rc;
-  g.items = sort.s.items[0];
-  HIPCHK(e, klf::launch_fs_compact(g, st, e->num_cus), "launch k_fs_compact");  // (nothing with n_hits = 0)
-  if (int rc = sort.digits()) return rc;
-  if (int rc = sort.passes(0, 8)) return rc;
-  HIPCHK(e, klf::launch_fs_rows(g, sort.sorted(), 1u, st), "launch k_fs_rows");
-  if (int rc = sort.passes(8, klf::kTlDigits)) return rc;
-  HIPCHK(e, klf::launch_fs_rows(g, sort.sorted(), 0u, st), "launch k_fs_rows");
-  // 4. one copy of the result block; segments -> stream ids; the all-streams counts and sum
-  std::vector<uint64_t> res(res_w);
-  if (int rc = sc.stop()) return rc;
-  HIPCHK(e, hipMemcpyAsync(res.data(), g.tab, res_w * 8, hipMemcpyDeviceToHost, st), "D2H field statistics");
-  HIPCHK(e, hipStreamSynchronize(st), "sync field statistics");
-  if (ms)
-    if (int rc = sc.elapsed(*ms)) return rc;
-  const std::vector<uint32_t> segstream = seg_streams(r);
-  const uint64_t* tab = res.data();
-  const klf::FsRow* drows = reinterpret_cast<const klf::FsRow*>(res.data() + tab_w + hpre_w);
-  const int64_t* dqv = reinterpret_cast<const int64_t*>(res.data() + tab_w + hpre_w + rows_w);
-  auto place = [&](klf_field_row& out, const klf::FsRow& d, __int128 sum) {
-    out.sum_lo = (uint64_t)(unsigned __int128)sum;
-    out.sum_hi = (int64_t)(sum >> 64);
-    if (!out.hits) return;
-    out.min = d.min;
-    out.max = d.max;
-    out.min_line = d.min_line;
-    out.max_line = d.max_line;
-    out.min_stream = d.min_seg < nsegs ? segstream[d.min_seg] : UINT32_MAX;
-    out.max_stream = d.max_seg < nsegs ? segstream[d.max_seg] : UINT32_MAX;
-  };
-  klf_field_row& all = rows[r->n_streams];
-  __int128 all_sum = 0;
-  for (uint32_t s = 0; s < nsegs; ++s) {
-    klf_field_row& out = rows[segstream[s]];
-    out.lines = tab[s];
-    out.hits = tab[(size_t)nsegs + s];
-    out.bad = tab[2 * (size_t)nsegs + s];
-    // the sum of v = (v >> 32) * 2^32 + (v & 0xFFFFFFFF) over the hits, from its two halves
-    const __int128 sum = (__int128)(int64_t)tab[3 * (size_t)nsegs + s] * ((__int128)1 << 32) + (__int128)tab[4 * (size_t)nsegs + s];
-    place(out, drows[s], sum);
-    if (nq) memcpy(qvals + (size_t)segstream[s] * nq, dqv + (size_t)s * nq, (size_t)nq * 8);
-    all.lines += out.lines;
-    all.hits += out.hits;
-    all.bad += out.bad;
-    all_sum += sum;
-  }
-  place(all, drows[nsegs], all_sum);
-  if (nq) memcpy(qvals + (size_t)r->n_streams * nq, dqv + (size_t)nsegs * nq, (size_t)nq * 8);
-  return KLF_OK;
-}
-
-extern "C" int klf_field_value(const uint8_t* content, size_t len, const uint8_t* key, uint32_t key_len,
-                               uint32_t decimals, uint32_t flags, int64_t* value) {
-  if ((!content && len) || !value || !field_opts_ok(key, key_len, decimals, flags)) return KLF_EINVAL;
-  *value = 0;
-  klf::FieldHostBytes src{content};
-  int64_t v = 0;
-  const int cls = klf::field_classify(src, (uint64_t)len, key, key_len, decimals, flags, &v);
-  if (cls == klf::kFieldHit) *value = v;
-  return cls;
 }
 
 extern "C" int klf_result_last_unparsed(klf_result* r, uint32_t id, uint64_t* rank) {

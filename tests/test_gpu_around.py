@@ -28,7 +28,7 @@ GZ = po.GO_ZERO_TIME
 COUNT_KEYS = ("lines", "parsed", "since_ok")
 NS = 10**9
 MS = 10**6
-AR_BLOCK = 2048  # anchors per block of the interval merge (klf_kernels.hpp kArBlock) and of a radix pass (kTlSortBlock)
+AR_BLOCK = 2048  # anchors per block of the interval merge (klf_analysis.hpp kArBlock) and of a radix pass (kTlSortBlock)
 
 
 def opt(t):

@@ -1,4 +1,4 @@
-"""The three consumers of the selected-line walk (klf_kernels.hip walk_publish / walk_rounds:
+"""The three consumers of the selected-line walk (klf_analysis.hip walk_publish / walk_rounds:
 k_tw_build, k_hist, k_tl_keys) held against each other on one batch: the window's selection, the
 histogram's table and the timeline's entries of the same result must describe the same lines, so
 a divergence of one of them fails here even where each still matches its own reference case."""

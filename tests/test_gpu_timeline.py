@@ -153,7 +153,7 @@ def test_key_range(gpu):
 
 @pytest.mark.parametrize("n", SORT_SIZES)
 def test_sort_sizes(gpu, n):
-    assert SORT_T == 2048  # klf_kernels.hpp kTlSortBlock: T - 1, T, T + 1 and 2 T + 1 are in the list
+    assert SORT_T == 2048  # klf_analysis.hpp kTlSortBlock: T - 1, T, T + 1 and 2 T + 1 are in the list
     with Session(sort_streams(n)) as s:
         ent = s.check()
         assert len(ent) == n

@@ -144,7 +144,7 @@ def digit_streams():
     return [b"".join(lines[k::3]) for k in range(3)]
 
 
-SORT_T = 2048  # the scatter's items per block (klf_kernels.hpp kTlSortBlock)
+SORT_T = 2048  # the scatter's items per block (klf_analysis.hpp kTlSortBlock)
 SORT_SIZES = (0, 1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, SORT_T - 1, SORT_T, SORT_T + 1, 4095, 4096, 4097,
               8191, 8192, 8193, 20000)
 assert 2 * SORT_T + 1 in SORT_SIZES
