@@ -278,6 +278,75 @@ int klf_around(klf_engine* e, klf_result* prev, const klf_around_opts* o, int64_
  * NULL. */
 int klf_result_around_info(const klf_result* r, uint64_t* anchors, uint64_t* intervals, double* build_ms);
 
+/* Multi-line records over the latest run (SPEC.md S4h; --record-*): a stack trace, a panic dump
+ * or a traceback reaches us as one parsed line per physical line; this call selects whole
+ * records, not single lines.  Per stream, over its parsed lines in input order, with C(l) = the
+ * S1 content of line l without its terminating '\n' (a '\r' stays; an unterminated trailing
+ * fragment counts like a terminated line):
+ * - a parsed line is a continuation by its content alone.  Default mode: KLF_RECORDS_INDENT is
+ *   set, C is non-empty and C[0] is ' ' or '\t'; or KLF_RECORDS_BLANK is set and C is empty; or C
+ *   starts with one of the prefixes (bytewise; a prefix longer than C does not match, one equal
+ *   to C does).  Head mode (KLF_RECORDS_PREFIX_HEAD; INDENT and BLANK must be clear): C starts
+ *   with none of the prefixes (typical ones: `{"level":`, `I0`, `E0`, `W0`, `20`).
+ * - every other parsed line is a head, and so is the first parsed line of a stream whatever its
+ *   content: orphan continuations at a stream's start form a record of their own and never join
+ *   the previous stream.  A record is a head plus the parsed lines behind it up to the next head
+ *   of the same stream.  Unparseable lines belong to no record, do not interrupt one (as
+ *   klf_regroup's context runs across them) and are never selected.
+ * - G' = the parsed lines of every record that holds at least one line of M; with
+ *   KLF_RECORDS_INVERT, of every record that holds none (grep -v at record level, not
+ *   KLF_REGROUP_INVERT's line-level S).  M is a subset of G' without invert, disjoint with it.
+ * - G'' = G' cut by [from, until) exactly as klf_window cuts (open bounds: no cut), afterwards: a
+ *   record whose match lies outside the window still contributes its lines inside it.  --since
+ *   and the tail rule with `tail` then run over G'' as they ran over M.
+ * counts.matched = |G''| per stream; lines / parsed / since_ok do not change;
+ * klf_result_match_bits stays M, klf_result_group_bits is G'', and the histogram, timeline, grouped
+ * counts and field statistics of the new result work on G''.  Degenerate settings are legal:
+ * default mode without flags and prefixes makes every line a head, and the call is
+ * klf_retail(prev, tail) over M byte for byte; head mode without prefixes makes each stream one
+ * record, selected whole if anything in it matched.
+ * The contract is klf_regroup's: prev must be the engine's latest result (KLF_ESTATE) and is
+ * stale afterwards.  The call always starts from M and never compounds: a klf_retail of the new
+ * result re-tails over G''; a klf_regroup, klf_window, klf_around or klf_records of it starts from
+ * M again; the next klf_run / klf_run_device is untouched.  Read again: M, the line meta, the
+ * line index (built now if the run left it out) and at most the first 32 content bytes of every
+ * parsed line in the batch, which must still be resident; no result depends on a byte outside a
+ * line's [start, end).  The scratch (a second bitmap of L/8 bytes and 64 bytes per 8192 lines) is
+ * freed before the call returns.  klf_result_timing [4] of the new result is the device time of
+ * building G' plus the tail stage's, as for klf_around.
+ * KLF_EINVAL (checked first, without touching the device, with a klf_last_error text where an
+ * engine is given): a null argument, tail < -1, unknown flag bits, INDENT or BLANK together with
+ * PREFIX_HEAD, a non-zero _reserved of a klf_time, nsec outside [0, 1e9), n_prefixes above
+ * KLF_RECORDS_MAX_PREFIXES, n_prefixes > 0 with null prefixes or prefix_off, offsets that do not
+ * ascend, an empty prefix or one longer than KLF_RECORDS_MAX_PREFIX, an engine without patterns.
+ * KLF_ENOMEM: the scratch does not fit.  Replaces nothing in the reference.  Out of scope: follow
+ * sessions and shard.run_split, as for klf_regroup; a cap on a record's length; regex or
+ * case-insensitive head rules; line context or --around combined with it in one call; a sparse
+ * variant that walks outward from the matches only. */
+#define KLF_RECORDS_INDENT 1u
+#define KLF_RECORDS_BLANK 2u
+#define KLF_RECORDS_PREFIX_HEAD 4u
+#define KLF_RECORDS_INVERT 8u
+#define KLF_RECORDS_MAX_PREFIXES 8u
+#define KLF_RECORDS_MAX_PREFIX 32u
+typedef struct klf_records_opts {
+  klf_time from, until;        /* [from, until), as klf_window_opts; open bounds = no cut */
+  const uint8_t* prefixes;     /* all prefixes concatenated; may be NULL iff n_prefixes == 0 */
+  const uint32_t* prefix_off;  /* n_prefixes + 1 offsets into prefixes, ascending */
+  uint32_t n_prefixes, flags;  /* KLF_RECORDS_* bits */
+} klf_records_opts;            /* 56 bytes */
+int klf_records(klf_engine* e, klf_result* prev, const klf_records_opts* o, int64_t tail, klf_result** out);
+/* On a klf_records result: the parsed lines classified head / continuation by content alone (the
+ * first-line rule not applied; heads + conts = the parsed lines of all streams) and the device
+ * time in ms of building G' alone; zeros on every other result, also on a klf_retail of a records
+ * result.  Each pointer may be NULL. */
+int klf_result_records_info(const klf_result* r, uint64_t* heads, uint64_t* conts, double* build_ms);
+/* Host helper, no GPU: the S4h class of one content (without its '\n'), by the classifier the
+ * kernels run (klf_recordcls.hpp): 1 = continuation, 0 = head.  from / until / KLF_RECORDS_INVERT
+ * of `o` are checked but do not bear on the class.  KLF_EINVAL: a null content with len > 0, a
+ * null o, or options klf_records refuses. */
+int klf_record_class(const uint8_t* content, size_t len, const klf_records_opts* o);
+
 /* ---- results -------------------------------------------------------------------- */
 /* Selected bytes of one stream (host view, D2H on first access; bytes == NULL: len and
  * counts only, no D2H). */
@@ -295,7 +364,8 @@ int klf_result_match_bits(klf_result* r, uint32_t stream_id, const uint8_t** bit
 /* Selection bitmap of one stream, packed like klf_result_match_bits: G' on a result of
  * klf_regroup (and on a klf_retail of one), M on every other result (klf_result_match_bits
  * returns M on all of them); G'' on a result of klf_window that cut or regrouped (and on a
- * klf_retail of one).  KLF_EINVAL when the engine has no patterns, except on a klf_window
+ * klf_retail of one), and on a result of klf_around or klf_records (and on a klf_retail of
+ * one).  KLF_EINVAL when the engine has no patterns, except on a klf_window
  * result (and a klf_retail of one): there it is G'', a subset of the parsed lines. */
 int klf_result_group_bits(klf_result* r, uint32_t stream_id, const uint8_t** bits,
                           uint64_t* nbytes);

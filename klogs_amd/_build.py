@@ -24,7 +24,8 @@ ARCH = os.environ.get("KLF_OFFLOAD_ARCH", "gfx950")
 
 ENGINE_SRCS = ["klf_kernels.hip", "klf_analysis.hip", "klf_engine.cpp", "klf_analysis.cpp", "klf_patterns.cpp"]
 ENGINE_HDRS = ["klf_kernels.hpp", "klf_analysis.hpp", "klf_device.hpp", "klf_engine_impl.hpp", "klf_patterns.hpp",
-               "klf_ts.hpp", "klf_groupkey.hpp", "klf_fieldval.hpp", "klf_copypool.hpp"]
+               "klf_ts.hpp", "klf_groupkey.hpp", "klf_fieldval.hpp", "klf_recordcls.hpp",
+               "klf_copypool.hpp"]
 MAX_COMPILE_JOBS = 16  # objects compiled at once, at most
 
 

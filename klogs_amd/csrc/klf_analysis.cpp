@@ -1,6 +1,7 @@
 // klf_analysis.cpp — the host halves of the calls on a finished run that make an object or a
 // table of their own: klf_result_histogram, klf_result_timeline, klf_result_groups,
-// klf_result_field_stats (SPEC.md S4c .. S4f), and klf_around's selection bitmap (S4g).  They read
+// klf_result_field_stats (SPEC.md S4c .. S4f), and klf_around's and klf_records' selection bitmaps
+// (S4g, S4h).  They read
 // the latest run's workspace through sel_view and launch the kernels of klf_analysis.hip; the run
 // itself, and the calls that end in its tail stage, are klf_engine.cpp's.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "klf_engine_impl.hpp"
 #include "klf_fieldval.hpp"
 #include "klf_groupkey.hpp"
+#include "klf_recordcls.hpp"
 
 using namespace klf_impl;
 
@@ -177,6 +179,70 @@ int klf_impl::around_build(klf_engine* e, const klf_result* prev, const klf_arou
   if (int rc = sc.alloc(g.iv, (size_t)k * sizeof(klf::ArIval), "intervals")) return rc;
   HIPCHK(e, klf::launch_ar_build(g, st, e->num_cus), "launch k_ar_build");
   return sc.finish(ms);
+}
+
+// klf_records' options (SPEC.md S4h): null when klf_records takes them, else what is wrong.
+static_assert(sizeof(klf_records_opts) == 56, "klf_records_opts layout");
+static_assert(KLF_RECORDS_INDENT == klf::kRecordsIndent && KLF_RECORDS_BLANK == klf::kRecordsBlank &&
+                  KLF_RECORDS_PREFIX_HEAD == klf::kRecordsPrefixHead && KLF_RECORDS_INVERT == klf::kRecordsInvert &&
+                  KLF_RECORDS_MAX_PREFIXES == klf::kRecordsMaxPrefixes && KLF_RECORDS_MAX_PREFIX == klf::kRecordsMaxPrefix,
+              "one set of values for the host helper and the kernels");
+const char* klf_impl::records_opts_error(const klf_records_opts* o) {
+  if (o->flags & ~(KLF_RECORDS_INDENT | KLF_RECORDS_BLANK | KLF_RECORDS_PREFIX_HEAD | KLF_RECORDS_INVERT))
+    return "unknown flag bits";
+  if ((o->flags & KLF_RECORDS_PREFIX_HEAD) && (o->flags & (KLF_RECORDS_INDENT | KLF_RECORDS_BLANK)))
+    return "KLF_RECORDS_INDENT / KLF_RECORDS_BLANK together with KLF_RECORDS_PREFIX_HEAD";
+  if (o->from._reserved || o->until._reserved) return "a non-zero _reserved";
+  if (o->from.nsec < 0 || o->from.nsec >= 1000000000 || o->until.nsec < 0 || o->until.nsec >= 1000000000)
+    return "nsec outside [0, 1e9)";
+  if (o->n_prefixes > KLF_RECORDS_MAX_PREFIXES) return "more than KLF_RECORDS_MAX_PREFIXES prefixes";
+  if (o->n_prefixes && (!o->prefixes || !o->prefix_off)) return "prefixes without their bytes or offsets";
+  for (uint32_t k = 0; k < o->n_prefixes; ++k) {
+    if (o->prefix_off[k + 1] < o->prefix_off[k]) return "prefix_off must ascend";
+    const uint32_t len = o->prefix_off[k + 1] - o->prefix_off[k];
+    if (len == 0 || len > KLF_RECORDS_MAX_PREFIX) return "a prefix must have 1 .. KLF_RECORDS_MAX_PREFIX bytes";
+  }
+  return nullptr;
+}
+
+// The prefixes of checked options, packed for the classifier.
+static klf::RecordPrefixes record_prefixes(const klf_records_opts* o) {
+  klf::RecordPrefixes p{};
+  for (uint32_t k = 0; k < o->n_prefixes; ++k)
+    klf::record_prefix_add(p, o->prefixes + o->prefix_off[k], o->prefix_off[k + 1] - o->prefix_off[k]);
+  return p;
+}
+
+// klf_records' selection bitmap (SPEC.md S4h; the kernels: klf_analysis.hpp, RecordArgs).  Four
+// kernels back to back; the host waits once, for the two counts.
+int klf_impl::records_build(klf_engine* e, const klf_result* prev, const klf_records_opts* o, double& ms,
+                            uint64_t& heads, uint64_t& conts) {
+  hipStream_t st = e->stream;
+  CallScratch sc(e, "klf_records", "records");
+  klf::RecordArgs g{};
+  g.v = sel_view(prev);
+  g.v.bits_in = e->d_bits.as<uint32_t>();  // M, whatever prev was selected from
+  g.pre = record_prefixes(o);
+  g.flags = o->flags;
+  g.bits_out = e->d_gbits.as<uint32_t>();
+  if (int rc = sc.alloc(g.start, (size_t)(g.v.cap_lines / 32 + 1) * 4, "start bitmap")) return rc;
+  if (int rc = sc.alloc(g.csum, (size_t)(g.v.nchunks + 1) * 8 * 8, "chunk sums")) return rc;
+  if (int rc = sc.alloc(g.counts, 16, "class counts")) return rc;
+  if (int rc = sc.start()) return rc;
+  HIPCHK(e, klf::launch_records(g, st, e->num_cus), "launch k_rc_heads .. k_rc_build");
+  if (int rc = sc.stop()) return rc;
+  uint64_t cnt[2] = {0, 0};
+  HIPCHK(e, hipMemcpyAsync(cnt, g.counts, 16, hipMemcpyDeviceToHost, st), "D2H class counts");
+  HIPCHK(e, hipStreamSynchronize(st), "sync records");
+  heads = cnt[0];
+  conts = cnt[1];
+  return sc.elapsed(ms);
+}
+
+extern "C" int klf_record_class(const uint8_t* content, size_t len, const klf_records_opts* o) {
+  if ((!content && len) || !o || klf_impl::records_opts_error(o)) return KLF_EINVAL;
+  const klf::RecordPrefixes p = record_prefixes(o);
+  return klf::record_class(klf::RecordHostLoad{}, content, (uint64_t)len, o->flags, p);
 }
 
 // Segment -> stream id.

@@ -1,6 +1,6 @@
-// klf_analysis.hip — the kernels of the calls on a finished run (SPEC.md S4a .. S4g): regroup,
+// klf_analysis.hip — the kernels of the calls on a finished run (SPEC.md S4a .. S4h): regroup,
 // time window, histogram, merged timeline and the device sort, grouped counts, field statistics,
-// time context across streams.  They read a finished run's line index, meta and bitmaps
+// time context across streams, multi-line records.  They read a finished run's line index, meta and bitmaps
 // (SelView) and write arrays of their own; none of them touches the run's device state, and
 // no kernel of the run (klf_kernels.hip) uses anything defined here.
 #include <hip/hip_runtime.h>
@@ -1351,6 +1351,186 @@ __global__ __launch_bounds__(256) void k_ar_build(ArArgs g) {
   }
 }
 
+// ======================================== multi-line records (klf_records, SPEC.md S4h) ==
+// G' = the parsed lines of every record that holds a line of M (inverted: that holds none).
+// k_rc_heads is the selected-line walk over the parsed lines, one lane per line: the classifier of
+// klf_recordcls.hpp over the line's content decides head or continuation, and the start bitmap
+// gets a bit on every head and on every segment's first line.  The other three kernels are a
+// segmented OR of M between start bits over the one sequence of all lines (klf_analysis.hpp,
+// RecordArgs): the shape of k_rg_sum / k_rg_carry / k_rg_build, on two bitmaps.
+
+// The kernel's loader for record_class: all 16 bytes of a block in one load.  It may reach 15
+// bytes past the content: into the next line, the next stream or the allocation's slack
+// (kAllocSlack); record_class masks them away before it compares.
+struct RcDevLoad {
+  __device__ __forceinline__ void operator()(const uint8_t* c, uint32_t blk, uint32_t, uint64_t& lo, uint64_t& hi) const {
+    typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+    u64x2 x;
+    __builtin_memcpy(&x, c + 16 * blk, 16);
+    lo = x.x;
+    hi = x.y;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_rc_heads(RecordArgs g) {
+  __shared__ WalkLds ws;
+  __shared__ uint32_t s_out[4][64];
+  __shared__ uint64_t s_cnt[2][4];
+  __shared__ RecordPrefixes s_pre;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  static_assert(sizeof(RecordPrefixes) % 4 == 0 && sizeof(RecordPrefixes) / 4 <= 256, "one word per thread");
+  if (t < (int)(sizeof(RecordPrefixes) / 4))
+    reinterpret_cast<uint32_t*>(&s_pre)[t] = reinterpret_cast<const uint32_t*>(&g.pre)[t];
+  SelView v = g.v;
+  v.bits_in = nullptr;  // the parsed lines
+  const uint64_t L = v.segout[v.nsegs - 1].line_hi;
+  const uint64_t nw = v.cap_lines / 32 + 1;  // words of the bitmaps
+  uint64_t heads = 0, conts = 0;             // the wave's (wave-uniform)
+  for (uint64_t c = blockIdx.x; c < v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t total = walk_publish(ws, v, view_word(v, w, L), l0);  // (the previous chunk's s_out is read)
+    uint32_t first = 0;  // the first line of every non-empty segment that begins in this word
+    if (l0 < L)
+      for (uint32_t s = find_seg_by_line(v.segout, v.nsegs, l0); s < v.nsegs; ++s) {
+        const uint64_t lo = v.segout[s].line_lo;
+        if (lo >= l0 + 32) break;
+        if (lo >= l0 && lo < v.segout[s].line_hi) first |= 1u << (lo - l0);
+      }
+    s_out[wv][lane] = first;
+    __syncthreads();  // (s_pre too)
+    walk_rounds(ws, v, total, l0, [&](const WalkLine& q) {
+      bool head = false;
+      if (q.live) {
+        const GrLine ln = sel_content(v, q.l, q.s);
+        head = record_class(RcDevLoad{}, ln.p, ln.n, g.flags, s_pre) == 0;
+        if (head) atomicOr(&s_out[wv][q.j], 1u << q.b);
+      }
+      const uint32_t nl = (uint32_t)__popcll(__ballot(q.live)), nh = (uint32_t)__popcll(__ballot(head));
+      heads += nh;
+      conts += nl - nh;
+    });
+    __syncthreads();
+    if (w < nw) g.start[w] = s_out[wv][lane];
+  }
+  if (lane == 0) { s_cnt[0][wv] = heads; s_cnt[1][wv] = conts; }
+  __syncthreads();
+  if (t == 0) {
+    fs_add(g.counts, s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3]);
+    fs_add(g.counts + 1, s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3]);
+  }
+}
+
+// Word w of M and of the start bitmap (0 past the line count; neither has a bit at or past L).
+__device__ __forceinline__ uint32_t rc_m_word(const RecordArgs& g, uint64_t w, uint64_t L) {
+  return w * 32 >= L ? 0u : g.v.bits_in[w] & word_range_mask(w, 0, L);
+}
+__device__ __forceinline__ uint32_t rc_s_word(const RecordArgs& g, uint64_t w, uint64_t L) {
+  return w * 32 >= L ? 0u : g.start[w] & word_range_mask(w, 0, L);
+}
+// The max-scan keys of a word x whose first line is l0: its last line + 1, ~(its first line); 0 = none.
+__device__ __forceinline__ uint64_t rc_last_key(uint32_t x, uint64_t l0) { return x ? l0 + (31 - __clz(x)) + 1 : 0; }
+__device__ __forceinline__ uint64_t rc_first_key(uint32_t x, uint64_t l0) { return x ? ~(l0 + (__ffs(x) - 1)) : 0; }
+
+__global__ __launch_bounds__(256) void k_rc_sum(RecordArgs g) {
+  __shared__ uint64_t s_w[4][4];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t m = rc_m_word(g, w, L), s = rc_s_word(g, w, L);
+    uint64_t k[4] = {rc_last_key(m, l0), rc_first_key(m, l0), rc_last_key(s, l0), rc_first_key(s, l0)};
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint64_t o = __shfl_xor(k[i], d, 64);
+        k[i] = k[i] > o ? k[i] : o;
+      }
+    __syncthreads();
+    if (lane == 0)
+      for (int i = 0; i < 4; ++i) s_w[i][wv] = k[i];
+    __syncthreads();
+    if (t < 4) {
+      uint64_t a = s_w[t][0];
+      for (int j = 1; j < 4; ++j) a = a > s_w[t][j] ? a : s_w[t][j];
+      g.csum[8 * c + t] = a;
+    }
+  }
+}
+
+// Thread t owns the chunks [t K, (t + 1) K), as in k_rg_carry: their maxima, a block scan for M's
+// keys and one for the start bitmap's, then each chunk's exclusive prefix / suffix.
+__global__ __launch_bounds__(256) void k_rc_carry(RecordArgs g) {
+  __shared__ uint64_t s_w[2][4];
+  const uint64_t K = (g.v.nchunks + 255) / 256;
+  const uint64_t c0 = threadIdx.x * K, c1 = c0 + K < g.v.nchunks ? c0 + K : g.v.nchunks;
+  uint64_t a[4] = {0, 0, 0, 0};
+  for (uint64_t c = c0; c < c1; ++c)
+    for (int i = 0; i < 4; ++i) {
+      const uint64_t x = g.csum[8 * c + i];
+      a[i] = a[i] > x ? a[i] : x;
+    }
+  uint64_t pre[2], post[2];
+  block_excl_scan_max64(a[0], a[1], s_w, &pre[0], &post[0]);
+  block_excl_scan_max64(a[2], a[3], s_w, &pre[1], &post[1]);
+  for (uint64_t c = c0; c < c1; ++c)
+    for (int i = 0; i < 2; ++i) {
+      g.csum[8 * c + 4 + 2 * i] = pre[i];
+      const uint64_t x = g.csum[8 * c + 2 * i];
+      pre[i] = pre[i] > x ? pre[i] : x;
+    }
+  for (uint64_t c = c1; c > c0; --c)
+    for (int i = 0; i < 2; ++i) {
+      g.csum[8 * (c - 1) + 5 + 2 * i] = post[i];
+      const uint64_t y = g.csum[8 * (c - 1) + 1 + 2 * i];
+      post[i] = post[i] > y ? post[i] : y;
+    }
+}
+
+// Occluded fills of a word: every bit of x spreads upwards (UP) or downwards over the following
+// lines that are not starts, so it stops ahead of a start bit going up and on one going down.
+template <bool UP>
+__device__ __forceinline__ uint32_t rc_fill(uint32_t x, uint32_t start) {
+  // p: the bits a neighbour's flag may enter: going up a line that is no start, going down the
+  // line below one that is no start
+  uint32_t p = UP ? ~start : ~start >> 1;
+#pragma unroll
+  for (uint32_t d = 1; d < 32; d <<= 1) {
+    x |= (UP ? x << d : x >> d) & p;
+    p &= UP ? p << d : p >> d;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(256) void k_rc_build(RecordArgs g) {
+  __shared__ uint64_t s_w[2][4];
+  const int t = threadIdx.x;
+  const uint64_t L = g.v.segout[g.v.nsegs - 1].line_hi;
+  const uint64_t nw = g.v.cap_lines / 32 + 1;  // words of the bitmaps
+  for (uint64_t c = blockIdx.x; c < g.v.nchunks; c += gridDim.x) {
+    const uint64_t w = c * (kMatchChunk / 32) + t, l0 = w * 32;
+    const uint32_t m = rc_m_word(g, w, L), s = rc_s_word(g, w, L);
+    const uint32_t pw = l0 < L ? meta_word<false>(g.v.meta, w, L) : 0u;  // (no bit at or past L)
+    // P + 1 of M and of the starts over the words before this one, ~N of both over the words after it
+    uint64_t pm, nm, ps, ns;
+    block_excl_scan_max64(rc_last_key(m, l0), rc_first_key(m, l0), s_w, &pm, &nm);
+    block_excl_scan_max64(rc_last_key(s, l0), rc_first_key(s, l0), s_w, &ps, &ns);
+    const uint64_t* cs = g.csum + 8 * c;
+    pm = pm > cs[4] ? pm : cs[4];
+    nm = nm > cs[5] ? nm : cs[5];
+    ps = ps > cs[6] ? ps : cs[6];
+    ns = ns > cs[7] ? ns : cs[7];
+    // the record open at the first line holds a match already: the last line of M before the
+    // word is at or behind the last start before it (the word's line 0 joins it unless it is a start)
+    const bool left = pm != 0 && pm >= ps;
+    // the record open at the last line gets one further on: ahead of the next start behind the word
+    const bool right = nm > ns;
+    uint32_t out = rc_fill<true>(m | (left ? ~s & 1u : 0u), s) | rc_fill<false>(m | (right ? 0x80000000u : 0u), s);
+    if (g.flags & kRecordsInvert) out = ~out;
+    if (w < nw) g.bits_out[w] = out & pw;
+  }
+}
+
 }  // namespace
 
 // The grid of a kernel that takes one kMatchChunk chunk per block turn: 16 blocks per CU at
@@ -1428,6 +1608,17 @@ hipError_t launch_ar_build(const ArArgs& g, hipStream_t st, int num_cus) {
   if (!nb || !g.k || !g.v.nchunks) return hipSuccess;
   if (hipError_t e = launch(k_ar_emit, dim3((uint32_t)nb), dim3(256), 0, st, g); e != hipSuccess) return e;
   return launch(k_ar_build, dim3(chunk_grid(g.v.nchunks, num_cus)), dim3(256), 0, st, g);
+}
+
+hipError_t launch_records(const RecordArgs& g, hipStream_t st, int num_cus) {
+  hipError_t e = hipMemsetAsync(g.start, 0, (size_t)(g.v.cap_lines / 32 + 1) * 4, st);
+  if (e == hipSuccess) e = hipMemsetAsync(g.counts, 0, 16, st);
+  if (e != hipSuccess || !g.v.nchunks) return e;
+  const uint32_t gc = chunk_grid(g.v.nchunks, num_cus);
+  if ((e = launch(k_rc_heads, dim3(gc), dim3(256), 0, st, g)) != hipSuccess) return e;
+  if ((e = launch(k_rc_sum, dim3(gc), dim3(256), 0, st, g)) != hipSuccess) return e;
+  if ((e = launch(k_rc_carry, dim3(1), dim3(256), 0, st, g)) != hipSuccess) return e;
+  return launch(k_rc_build, dim3(gc), dim3(256), 0, st, g);
 }
 
 hipError_t launch_tl_plan(const TlArgs& g, uint32_t which, hipStream_t st) {

@@ -1,9 +1,10 @@
 // klf_analysis.hpp — argument structs and host launchers of the calls on a finished run
-// (SPEC.md S4a .. S4g).  Kernels live in klf_analysis.hip; the host halves are in klf_analysis.cpp
-// and, for the calls that end in the run's tail stage (klf_regroup, klf_window, klf_around), in
-// klf_engine.cpp.
+// (SPEC.md S4a .. S4h).  Kernels live in klf_analysis.hip; the host halves are in klf_analysis.cpp
+// and, for the calls that end in the run's tail stage (klf_regroup, klf_window, klf_around,
+// klf_records), in klf_engine.cpp.
 #pragma once
 #include "klf_kernels.hpp"
+#include "klf_recordcls.hpp"
 
 namespace klf {
 
@@ -281,6 +282,42 @@ struct ArArgs {
 hipError_t launch_ar_heads(const ArArgs& g, hipStream_t stream);
 // k_ar_emit into g.iv, then k_ar_build into g.bits_out (every word of it).  Nothing with K = 0.
 hipError_t launch_ar_build(const ArArgs& g, hipStream_t stream, int num_cus);
+
+// Multi-line records over a finished run (klf_records, SPEC.md S4h): G' = the parsed lines of
+// every record (a head and the parsed lines behind it up to the next head of its stream) that
+// holds a line of M; inverted: that holds none.
+//   k_rc_heads                the selected-line walk over the parsed lines, one lane per line: the
+//                             classifier of klf_recordcls.hpp over at most the first 32 content
+//                             bytes; the start bitmap = the heads and every segment's first line;
+//                             heads / continuations counted, one atomic pair per block
+//   k_rc_sum / k_rc_carry / k_rc_build   the segmented OR of M between start bits.  A start bit on
+//                             every segment's first line keeps records inside their streams, so
+//                             the three kernels see one sequence of L lines.  Carries are kept
+//                             like k_rg_*'s, as max-scan keys of line positions: P + 1 (0 = none)
+//                             of the last, ~N (0 = none) of the first line of M and of the start
+//                             bitmap before / after a word.  The record open at a word's first
+//                             line already holds a match iff P_M >= P_start; the one open at its
+//                             last line gets one further on iff N_M < N_start.  A word or chunk
+//                             without a start passes both through by construction.  Inside a
+//                             word two occluded fills (five doubling steps each) spread M and the
+//                             two carries up and down to the next start bit.
+// The cost beside the walk's own reads is 4 x L/8 + 2L bytes read and 2 x L/8 written.  No
+// kernel waits on another block: kernel boundaries are the only ordering.
+struct RecordArgs {
+  SelView v;                // bits_in = M, never null (k_rc_heads walks the parsed lines)
+  RecordPrefixes pre;       // the caller's prefixes, by value
+  uint32_t flags;           // klf_records_opts
+  uint32_t* start;          // [cap_lines / 32 + 1] the start bitmap, the layout of M (zeroed by launch_records)
+  uint32_t* bits_out;       // G', same layout
+  // per kMatchChunk chunk c: [0] last line of M in the chunk + 1 (0 = none), [1] ~(its first
+  // line) (0 = none), [2] / [3] the same of the start bitmap; then [4] / [5] = [0] over the
+  // chunks before c / [1] over the chunks after c, and [6] / [7] = [2] / [3] likewise;
+  // 8 * nchunks u64
+  uint64_t* csum;
+  uint64_t* counts;         // [2] heads, continuations (zeroed by launch_records)
+};
+// Zeroes g.start and g.counts, then k_rc_heads, k_rc_sum, k_rc_carry, k_rc_build into g.bits_out.
+hipError_t launch_records(const RecordArgs& g, hipStream_t stream, int num_cus);
 
 // Zeroes g.table and counts into it (k_hist).
 hipError_t launch_hist(const HistArgs& g, hipStream_t stream, int num_cus);

@@ -1560,6 +1560,8 @@ extern "C" int klf_run_device(klf_engine* e, const uint8_t* d_bytes, uint32_t n,
 // G' only when o asks for context or inversion, then cut by the time window when a bound is
 // closed or the engine has no patterns; always from M).  klf_around (ar, with tw holding its
 // bounds and no context): G' from the anchors' time intervals (around_build), then the same cut.
+// klf_records (rc, with tw holding its bounds): G' from the records' heads (records_build), then
+// the same cut.
 static bool window_closed(const klf_window_opts* tw) {
   return tw->from.sec != KLF_TIME_MIN_SEC || tw->until.sec != KLF_TIME_MAX_SEC;
 }
@@ -1577,7 +1579,8 @@ klf::SelView klf_impl::sel_view(const klf_result* r) {
 }
 
 static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* o, int64_t tail, klf_result** out,
-                       const char* what, const klf_window_opts* tw = nullptr, const klf_around_opts* ar = nullptr) {
+                       const char* what, const klf_window_opts* tw = nullptr, const klf_around_opts* ar = nullptr,
+                       const klf_records_opts* rc = nullptr) {
   if (int rc = check_latest(e, prev, what)) return rc;
   if (int rc = ensure_index(e)) return rc;
   HIPCHK(e, hipSetDevice(e->device), "hipSetDevice");
@@ -1592,7 +1595,7 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
   // bitmap mode, over d_gbits, like a regrouped result)
   const bool regroup = o && (!tw || o->before || o->after || o->flags);
   const bool cut = tw && (window_closed(tw) || !prev->has_bits);
-  r->grouped = (o || tw) ? (regroup || cut || ar) : prev->grouped;
+  r->grouped = (o || tw) ? (regroup || cut || ar || rc) : prev->grouped;
   r->total_lines = prev->total_lines;
   r->counted = prev->counted;
   r->pcount_ok = prev->pcount_ok;
@@ -1633,6 +1636,13 @@ static int retail_impl(klf_engine* e, klf_result* prev, const klf_regroup_opts* 
         if (int rc = around_build(e, prev, ar, build_ms, r->ar_anchors, r->ar_intervals)) { delete r; return rc; }
       a.bits = e->d_gbits.as<uint32_t>();
       r->ar_build_ms = build_ms;
+    }
+    if (rc) {  // (a bracket of its own, like klf_around's: it reads its two counts back)
+      h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
+      if (h == hipSuccess)
+        if (int err = records_build(e, prev, rc, build_ms, r->rc_heads, r->rc_conts)) { delete r; return err; }
+      a.bits = e->d_gbits.as<uint32_t>();
+      r->rc_build_ms = build_ms;
     }
     if (cut) {
       if (h == hipSuccess) h = e->d_gbits.ensure((a.cap_lines / 32 + 1) * 4);
@@ -1717,6 +1727,25 @@ extern "C" int klf_around(klf_engine* e, klf_result* prev, const klf_around_opts
   if (!prev->has_bits) return set_err(e, KLF_EINVAL, "klf_around: the engine has no patterns");
   const klf_window_opts w{o->from, o->until, 0, 0, 0, 0};
   return retail_impl(e, prev, nullptr, tail, out, "klf_around", &w, o);
+}
+
+extern "C" int klf_records(klf_engine* e, klf_result* prev, const klf_records_opts* o, int64_t tail, klf_result** out) {
+  if (!o || !out || tail < -1) return KLF_EINVAL;
+  *out = nullptr;
+  if (const char* bad = records_opts_error(o))  // (the options first: they need neither an engine nor a device)
+    return e ? set_err(e, KLF_EINVAL, std::string("klf_records: ") + bad) : KLF_EINVAL;
+  if (!e || !prev || prev->e != e) return KLF_EINVAL;
+  if (!prev->has_bits) return set_err(e, KLF_EINVAL, "klf_records: the engine has no patterns");
+  const klf_window_opts w{o->from, o->until, 0, 0, 0, 0};
+  return retail_impl(e, prev, nullptr, tail, out, "klf_records", &w, nullptr, o);
+}
+
+extern "C" int klf_result_records_info(const klf_result* r, uint64_t* heads, uint64_t* conts, double* build_ms) {
+  if (!r) return KLF_EINVAL;
+  if (heads) *heads = r->rc_heads;
+  if (conts) *conts = r->rc_conts;
+  if (build_ms) *build_ms = r->rc_build_ms;
+  return KLF_OK;
 }
 
 extern "C" int klf_result_around_info(const klf_result* r, uint64_t* anchors, uint64_t* intervals, double* build_ms) {

@@ -232,6 +232,8 @@ struct klf_result {
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t ar_anchors = 0, ar_intervals = 0;  // a klf_around result: |A| and the merged intervals K,
   double ar_build_ms = 0.0;                   // and the device time of building G' (part of ms[4])
+  uint64_t rc_heads = 0, rc_conts = 0;        // a klf_records result: the parsed lines by class,
+  double rc_build_ms = 0.0;                   // and the device time of building G' (part of ms[4])
   uint32_t ev_mask = 0;              // the timing events the run recorded
   int index_mode = KLF_INDEX_FULL;   // how much of the line index the run itself wrote
   // lazily filled host copies
@@ -278,6 +280,12 @@ int ensure_index(klf_engine* e);
 // build's device time, n / k = the anchors and their merged intervals.  (klf_analysis.cpp)
 int around_build(klf_engine* e, const klf_result* prev, const klf_around_opts* o, double& ms, uint64_t& n,
                  uint64_t& k);
+// What is wrong with klf_records' options, or null (no engine, no device).  (klf_analysis.cpp)
+const char* records_opts_error(const klf_records_opts* o);
+// Builds klf_records' G' into e->d_gbits (sized by the caller) from the latest run's M; ms = the
+// build's device time, heads / conts = the parsed lines by class.  (klf_analysis.cpp)
+int records_build(klf_engine* e, const klf_result* prev, const klf_records_opts* o, double& ms, uint64_t& heads,
+                  uint64_t& conts);
 
 // Device bytes -> a file descriptor (klf_result_write, klf_timeline_write).
 constexpr size_t kStageChunk = 64u << 20;  // pinned staging chunk = device chunk

@@ -4,6 +4,8 @@
 //   klogs-filter [-p logpath] [-s since] [-t tail] [-i] [--grep LIT]... [--match RE]...
 //                [-A N] [-B N] [-C N] [--invert-match] [--from X] [--until X] [--histogram WIDTH]
 //                [--around D] [--around-before D] [--around-after D]
+//                [--record-indent] [--record-blank] [--record-cont PREFIX]... [--record-head PREFIX]...
+//                [--record-invert]
 //                [--merge [--merge-timestamps]] [--top K [--top-mask-digits] [--top-key-bytes N]]
 //                [--stat KEY [--stat-decimals D | --stat-duration]]
 //                [--now UNIX_SEC[.NSEC]] [--device N] [--no-color] MANIFEST
@@ -23,6 +25,16 @@
 // reach ahead of / behind a match alone and override --around.  They need a --grep or --match,
 // exclude -A / -B / -C / --invert-match, and combine with --from / --until (the cut is made
 // after the context is taken), --since, --tail, --merge, --histogram, --top and --stat.
+//
+// --record-* select whole multi-line records (SPEC.md S4h, klf_records): a stack trace, a panic
+// dump or a traceback goes out with the line that matched, and nothing behind it does.  A record
+// is a head line and the continuation lines behind it.  A line continues a record when it begins
+// with a space or a tab (--record-indent), is empty (--record-blank) or begins with a --record-cont
+// PREFIX; or, with --record-head PREFIX given, when it begins with none of them (the other three
+// are then refused).  Up to 8 prefixes of 1..32 bytes.  --record-invert keeps the records without
+// a match.  Any of the flags turns the stage on.  They need a --grep or --match, exclude -A / -B /
+// -C / --invert-match / --around*, and combine with --from / --until (the cut is made after the
+// records are taken), --since, --tail, --merge, --histogram, --top and --stat.
 //
 // --histogram WIDTH (a Go duration > 0) also writes <logpath>/histogram.tsv: per stream, the
 // lines of the selection (after the pattern, the context flags and the window; before --since
@@ -103,6 +115,12 @@ void usage() {
                "                    the lines of every container within D, a duration >= 0, of a matching line of\n"
                "                    any container; ahead of / behind a match alone; not with -A / -B / -C /\n"
                "                    --invert-match)\n"
+               "                    [--record-indent] [--record-blank] [--record-cont PREFIX]... [--record-head PREFIX]...\n"
+               "                    [--record-invert]   (with --grep / --match: whole multi-line records, a head\n"
+               "                    line and the lines behind it that begin with a space or tab / are empty / begin\n"
+               "                    with PREFIX; or, with --record-head, that begin with none of its PREFIXes; the\n"
+               "                    records without a match; up to 8 prefixes of 1..32 bytes; not with -A / -B / -C /\n"
+               "                    --invert-match / --around*)\n"
                "                    [--histogram WIDTH]   (also writes <logpath>/histogram.tsv: the selected lines\n"
                "                    per stream in buckets of WIDTH, a duration > 0, from --from (else the --since\n"
                "                    instant; one of them is needed) up to --until (else --now), at most 65536\n"
@@ -138,6 +156,9 @@ int main(int argc, char** argv) {
   bool from_set = false, until_set = false;  // --from / --until
   std::string around_arg, around_before_arg, around_after_arg;
   bool around_set = false, around_before_set = false, around_after_set = false;  // --around, -before, -after
+  uint32_t record_flags = 0;  // --record-indent, --record-blank, --record-invert
+  std::vector<std::string> record_cont, record_head;  // --record-cont, --record-head
+  bool recorded = false;  // any --record-*
   std::string hist_arg;
   bool hist_set = false;  // --histogram
   bool merge = false, merge_ts = false;  // --merge, --merge-timestamps
@@ -180,6 +201,11 @@ int main(int argc, char** argv) {
     else if (a == "--around") { around_arg = val(); around_set = true; }
     else if (a == "--around-before") { around_before_arg = val(); around_before_set = true; }
     else if (a == "--around-after") { around_after_arg = val(); around_after_set = true; }
+    else if (a == "--record-indent") { record_flags |= KLF_RECORDS_INDENT; recorded = true; }
+    else if (a == "--record-blank") { record_flags |= KLF_RECORDS_BLANK; recorded = true; }
+    else if (a == "--record-invert") { record_flags |= KLF_RECORDS_INVERT; recorded = true; }
+    else if (a == "--record-cont") { record_cont.push_back(val()); recorded = true; }
+    else if (a == "--record-head") { record_head.push_back(val()); recorded = true; }
     else if (a == "--histogram") { hist_arg = val(); hist_set = true; }
     else if (a == "--merge") merge = true;
     else if (a == "--merge-timestamps") merge_ts = true;
@@ -207,6 +233,8 @@ int main(int argc, char** argv) {
   if (regrouped && greps.empty() && matches.empty()) usage();  // context / inversion of what?
   const bool around = around_set || around_before_set || around_after_set;
   if (around && ((greps.empty() && matches.empty()) || regrouped)) usage();  // around what? / no line context with it
+  if (recorded && ((greps.empty() && matches.empty()) || regrouped || around)) usage();  // records of what? / one transform a call
+  if (!record_head.empty() && (!record_cont.empty() || (record_flags & (KLF_RECORDS_INDENT | KLF_RECORDS_BLANK)))) usage();
   if (merge_ts && !merge) usage();
   if ((top_set && top.top == 0) || ((top_mask || top_key_set) && !top_set)) usage();
   if (top_mask) top.flags |= KLF_GROUPS_MASK_DIGITS;
@@ -241,6 +269,20 @@ int main(int argc, char** argv) {
   if (around_set) around_opts.before_ns = around_opts.after_ns = reach(around_arg);
   if (around_before_set) around_opts.before_ns = reach(around_before_arg);
   if (around_after_set) around_opts.after_ns = reach(around_after_arg);
+  // --record-*: the prefixes of the one mode, concatenated; the bounds ride along
+  const std::vector<std::string>& record_pre = record_head.empty() ? record_cont : record_head;
+  if (record_pre.size() > KLF_RECORDS_MAX_PREFIXES) usage();
+  std::string record_bytes;
+  std::vector<uint32_t> record_off{0};
+  for (const std::string& p : record_pre) {
+    if (p.empty() || p.size() > KLF_RECORDS_MAX_PREFIX) usage();
+    record_bytes += p;
+    record_off.push_back((uint32_t)record_bytes.size());
+  }
+  const klf_records_opts records_opts{window.from, window.until,
+                                      record_pre.empty() ? nullptr : (const uint8_t*)record_bytes.data(),
+                                      record_pre.empty() ? nullptr : record_off.data(), (uint32_t)record_pre.size(),
+                                      record_flags | (record_head.empty() ? 0u : KLF_RECORDS_PREFIX_HEAD)};
   if (logpath.empty()) {  // defaultLogPath (:47)
     char buf[128];
     klh_default_log_path(now.sec, buf, sizeof(buf));
@@ -361,13 +403,19 @@ int main(int argc, char** argv) {
     // context / inversion: the run itself with --tail 0 (the cheapest run that leaves the
     // line index and the match bitmap behind), then klf_regroup applies the user's tail
     const int64_t user_tail = filter.tail;
-    if (regrouped || windowed || around) filter.tail = 0;
+    if (regrouped || windowed || around || recorded) filter.tail = 0;
     rc = klf_run(e, &filter, &r);
     if (rc != KLF_OK) panic_exit(std::string("klf_run: ") + klf_strerror(rc) + ": " + klf_last_error(e));
     if (around) {  // (with the window, if any, in the one call)
       klf_result* g = nullptr;
       rc = klf_around(e, r, &around_opts, user_tail, &g);
       if (rc != KLF_OK) panic_exit(std::string("klf_around: ") + klf_strerror(rc) + ": " + klf_last_error(e));
+      klf_result_free(r);
+      r = g;
+    } else if (recorded) {  // (with the window, if any, in the one call)
+      klf_result* g = nullptr;
+      rc = klf_records(e, r, &records_opts, user_tail, &g);
+      if (rc != KLF_OK) panic_exit(std::string("klf_records: ") + klf_strerror(rc) + ": " + klf_last_error(e));
       klf_result_free(r);
       r = g;
     } else if (windowed) {  // (with the context flags, if any, in the one call)

@@ -31,6 +31,9 @@ GO_ZERO_TIME = (-62135596800, 0)
 TIME_MIN_SEC = -(1 << 63)     # KLF_TIME_MIN_SEC: klf_window_opts.from.sec, open below
 TIME_MAX_SEC = (1 << 63) - 1  # KLF_TIME_MAX_SEC: klf_window_opts.until.sec, open above
 AROUND_MAX_NS = (1 << 62) - 1  # KLF_AROUND_MAX_NS: klf_around_opts.before_ns / after_ns at most
+RECORDS_INDENT, RECORDS_BLANK, RECORDS_PREFIX_HEAD, RECORDS_INVERT = 1, 2, 4, 8  # KLF_RECORDS_* flag bits
+RECORDS_MAX_PREFIXES = 8      # KLF_RECORDS_MAX_PREFIXES: klf_records_opts.n_prefixes at most
+RECORDS_MAX_PREFIX = 32       # KLF_RECORDS_MAX_PREFIX: bytes of one prefix at most
 HIST_MAX_BUCKETS = 65536      # KLF_HIST_MAX_BUCKETS: klf_hist_opts.n_buckets at most
 TIMELINE_TIMESTAMPS = 1       # KLF_TIMELINE_TIMESTAMPS: render each line's prefix too
 TIMELINE_MAX_TAG = 1024       # KLF_TIMELINE_MAX_TAG: bytes of one stream's tag at most
@@ -80,6 +83,11 @@ class _WindowOpts(C.Structure):
 class _AroundOpts(C.Structure):  # klf_around_opts (56 bytes)
     _fields_ = [("from_", _Time), ("until", _Time), ("before_ns", C.c_uint64), ("after_ns", C.c_uint64),
                 ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class _RecordsOpts(C.Structure):  # klf_records_opts (56 bytes)
+    _fields_ = [("from_", _Time), ("until", _Time), ("prefixes", C.c_void_p), ("prefix_off", C.c_void_p),
+                ("n_prefixes", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class _HistOpts(C.Structure):
@@ -153,6 +161,10 @@ SIGNATURES = {
     "klf_around": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_AroundOpts), C.c_int64, C.POINTER(C.c_void_p)]),
     "klf_result_around_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_double)]),
+    "klf_records": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_RecordsOpts), C.c_int64, C.POINTER(C.c_void_p)]),
+    "klf_result_records_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_double)]),
+    "klf_record_class": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_RecordsOpts)]),
     "klf_result_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                     C.POINTER(_Counts)]),
     "klf_result_lines": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -452,6 +464,49 @@ def field_value(content: bytes, key: bytes, decimals: int = 0, duration: bool = 
     if rc < 0:
         _check(rc)
     return rc, int(v.value)
+
+
+def records_opts(indent: bool = False, blank: bool = False, cont: Sequence[bytes] = (), head: Sequence[bytes] = (),
+                 invert: bool = False, from_: Optional[Tuple[int, int]] = None,
+                 until: Optional[Tuple[int, int]] = None, flags: Optional[int] = None):
+    """(klf_records_opts, the buffers it points into) of `Result.records`' arguments.  `head`
+    non-empty selects head mode; with `cont`, `indent` or `blank` beside it: ValueError.  flags:
+    the raw KLF_RECORDS_* bits instead, with `cont` (or `head`) as the prefixes."""
+    cont, head = [bytes(p) for p in cont], [bytes(p) for p in head]
+    if head and (cont or indent or blank):
+        raise ValueError("records: head prefixes exclude cont, indent and blank")
+    pre = head or cont
+    o = _RecordsOpts()
+    lo = (TIME_MIN_SEC, 0) if from_ is None else from_
+    hi = (TIME_MAX_SEC, 0) if until is None else until
+    o.from_.sec, o.from_.nsec = int(lo[0]), int(lo[1])
+    o.until.sec, o.until.nsec = int(hi[0]), int(hi[1])
+    if flags is None:
+        flags = ((RECORDS_INDENT if indent else 0) | (RECORDS_BLANK if blank else 0) |
+                 (RECORDS_PREFIX_HEAD if head else 0) | (RECORDS_INVERT if invert else 0))
+    o.flags = int(flags)
+    o.n_prefixes = len(pre)
+    blob = b"".join(pre)
+    buf = C.create_string_buffer(blob, len(blob) or 1)
+    off = (C.c_uint32 * (len(pre) + 1))()
+    for k, p in enumerate(pre):
+        off[k + 1] = off[k] + len(p)
+    if pre:
+        o.prefixes, o.prefix_off = C.addressof(buf), C.addressof(off)
+    return o, (buf, off)
+
+
+def record_class(content: bytes, indent: bool = False, blank: bool = False, cont: Sequence[bytes] = (),
+                 head: Sequence[bytes] = ()) -> int:
+    """klf_record_class: 1 when the content (without its '\\n') is a continuation by SPEC.md S4h, 0
+    when it is a head, from the classifier the kernels run.  No GPU."""
+    content = bytes(content)
+    o, keep = records_opts(indent, blank, cont, head)
+    src = C.create_string_buffer(content, len(content) or 1)
+    rc = _lib.klf_record_class(C.addressof(src), len(content), C.byref(o))
+    if rc < 0:
+        _check(rc)
+    return rc
 
 
 class Groups:
@@ -791,6 +846,29 @@ class Result:
         ms = C.c_double()
         _check(_lib.klf_result_around_info(self._p, None, None, C.byref(ms)))
         return float(ms.value)
+
+    def records(self, indent: bool = False, blank: bool = False, cont: Sequence[bytes] = (),
+                head: Sequence[bytes] = (), invert: bool = False, from_: Optional[Tuple[int, int]] = None,
+                until: Optional[Tuple[int, int]] = None, tail: int = -1, flags: Optional[int] = None) -> "Result":
+        """The same run with whole multi-line records selected (klf_records, SPEC.md S4h): every
+        parsed line of each record that holds a match (invert: that holds none), a record being a
+        head line and the continuation lines behind it.  A line continues a record when it is
+        indented (`indent`), empty (`blank`) or starts with one of `cont`; with `head` given, when
+        it starts with none of `head`.  Then cut to [from_, until) as `window` cuts, then --since
+        and --tail N.  Always from the run's own matches.  This result is stale afterwards.  flags:
+        the raw KLF_RECORDS_* bits instead, with `cont` (or `head`) as the prefixes."""
+        o, keep = records_opts(indent, blank, cont, head, invert, from_, until, flags)
+        r = C.c_void_p()
+        _check(_lib.klf_records(self._eng._h, self._p, C.byref(o), int(tail), C.byref(r)), self._eng._h)
+        return Result(r.value or 0, self.n_streams, self._eng)
+
+    def records_info(self) -> Tuple[int, int, float]:
+        """klf_result_records_info: (heads, continuations, build ms) of a `records` result: the
+        parsed lines by class (by content alone) and the device time of building the selection
+        (part of timing()[4])."""
+        h, c, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        _check(_lib.klf_result_records_info(self._p, C.byref(h), C.byref(c), C.byref(ms)))
+        return int(h.value), int(c.value), float(ms.value)
 
     def free(self):
         if self._p:
